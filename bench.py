@@ -11,6 +11,9 @@ models/srmodel.py:145-171).  `value` = LR patches/s over all ranks with inputs r
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
+`--steps K` is the number of timed steps and `ms_per_step` the time of one of them.  `--dump-outputs DIR` writes what the last
+timed step computed to DIR/*.npy (dump_outputs), so that two builds run with the same arguments can be compared output for output.
+
 Rank 0 prints ONE JSON line.  Extra objects: `roofline` (the dominant kernel, the 64->64 3x3 implicit-GEMM
 conv, timed with HIP events on its own stream inside this process) and, at N=1, `cpu_baseline` (the CPU
 oracle's training step timed on this host's cores over a bounded sample).
@@ -65,7 +68,12 @@ def parse():
     p.add_argument("--no-roofline", action="store_true")
     p.add_argument("--no-other-configs", action="store_true",
                    help="skip the batch-16 runs of the five BASELINE models that follow the timed region of the default line")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", metavar="DIR",
+                   help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all; see dump_outputs)")
+    a = p.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def spawn_ranks(a):
@@ -647,6 +655,39 @@ def dominant_kernel_roofline(A, model_name, batch, patch, feats, dtype, iters=10
     return r
 
 
+DUMP_SHARE = {"loss": 1 << 10, "sr": 28 << 20, "params": 14 << 20, "grads": 14 << 20}     # bytes per array: under 64 MB in all
+
+
+def _dump_sample(x, cap, rows):
+    """`x` cut to at most `cap` elements by a sample that depends on its shape alone (the same elements on every run and build):
+    whole entries of dim 0 (images) when `rows`, single elements otherwise."""
+    if x.numel() <= cap:
+        return x
+    g = torch.Generator().manual_seed(0)
+    if rows and x.dim() > 1 and x[0].numel() <= cap:
+        idx = torch.randperm(x.shape[0], generator=g)[:cap // x[0].numel()].sort().values
+        return x[idx.to(x.device)]
+    idx = torch.randperm(x.numel(), generator=g)[:cap].sort().values
+    return x.reshape(-1)[idx.to(x.device)]
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each tensor of `arrays` as path/<name>.npy in float32, cut to its DUMP_SHARE by _dump_sample.  What main()
+    passes, copied right after the last timed step: training -- `loss`, `sr` (the model's output; absent when the timed steps are
+    the trainer's segmented-overlap step, whose forward output bench.py cannot reach), `params` (every trainable parameter after the
+    step, flattened and concatenated in named_parameters() order; with several ranks' optimizer-first graph the update is still
+    pending, so the weights the step ran with) and `grads` (their gradients from the step, same layout); inference -- `sr`.
+    Returns {name: shape written}."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    shapes = {}
+    for name, x in arrays.items():
+        y = _dump_sample(x.detach(), DUMP_SHARE[name] // 4, rows=(name == "sr")).float().cpu().numpy()
+        np.save(os.path.join(path, f"{name}.npy"), y)
+        shapes[name] = list(y.shape)
+    return shapes
+
+
 def executed_gflop_fwd(model_name, gflop_fwd, patch, scale, dtype, collapsed):
     """Conv GFLOP per patch the HIP path EXECUTES in a forward pass.  The reference's module graph ends EDSR / RCAN /
     RDN with conv3x3(64 -> 256) -> PixelShuffle(2) -> conv3x3(64 -> 3); on the 16-bit path those two layers run as ONE 5x5 convolution
@@ -805,6 +846,8 @@ def main():
     def fwd_bwd():
         opt.zero_grad(set_to_none=True)
         sr = net(batch["lr"])
+        if a.dump_outputs:
+            last["sr"] = sr             # held so that a captured step's output buffer is not reused by its backward pass
         loss = model._calculate_losses(img_sr=sr, img_hr=batch["hr"])["loss"]
         A.ops.backward(loss if scaler is None else scaler.scale(loss))
         return loss
@@ -848,6 +891,10 @@ def main():
             graphs, mode = None, "eager"
             step = (lambda: ogs.eager_step(batch)) if (ogs is not None and ogs.gsync is not None) else step
             torch.cuda.synchronize()
+        if graphs is not None or step is not train_step:
+            # the timed steps are the trainer's (captured or eager), whose forward output bench.py cannot reach: drop the one the
+            # eager steps above left, so that a dump carries no output of another step
+            last.pop("sr", None)
     elif mode != "eager":
         try:
             with torch.cuda.stream(side):
@@ -921,6 +968,20 @@ def main():
     loss_first = float(last["out"].detach().float().mean()) if not a.inference and "out" in last else None
     el = timed(a.steps)
     loss_last = float(last["out"].detach().float().mean()) if not a.inference and "out" in last else None
+    # --dump-outputs: device copies of the last timed step's results, taken here (queued on the stream behind that step, before any
+    # later replay) and written after the sustained window, so that the host-side work of the dump does not sit between the two windows
+    snap, dumped = None, None
+    if a.dump_outputs and rank == 0:
+        if a.inference:
+            snap = {"sr": last["out"].detach().clone()}
+        else:
+            snap = {"loss": last["out"].detach().clone()}
+            if "sr" in last:                # (not with the trainer's segmented-overlap step: see above)
+                snap["sr"] = last["sr"].detach().clone()
+            snap["params"] = torch.cat([p.detach().reshape(-1).float() for p in params])
+            if all(p.grad is not None for p in params):
+                snap["grads"] = torch.cat([p.grad.detach().reshape(-1).float() for p in params])
+    last.pop("sr", None)
     # sustained rate: the chip lowers its clock under this kernel within ~1 s; the driver's K steps
     # are a burst.  The number of extra steps is fixed from the timed rate so that every rank runs the same count.
     sustained = None
@@ -931,6 +992,9 @@ def main():
             dist.broadcast(t, src=0)
             ns = int(t.item())
         sustained = timed(ns) / ns
+    if snap is not None:
+        dumped = dump_outputs(a.dump_outputs, snap)
+        del snap
 
     # the collective alone (all buckets back to back, every rank), HIP events on the launch stream: what a step exposes when nothing
     # overlaps it -- so that the first multi-GPU run explains itself (`config.allreduce_ms`, `config.rccl_ranks`)
@@ -972,6 +1036,8 @@ def main():
         out["config"]["hr_stage"] = ("collapsed: conv3x3(64->256) + PixelShuffle(2) + conv3x3(64->3) as one 5x5 conv 64->12 with exact border terms "
                                      "(ops.hr_tail; SRK_NO_HR_COLLAPSE=1 = layer by layer)"
                                      if (gx != flop_per_patch) else "layer by layer")
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": a.dump_outputs, "shapes": dumped}
         if scaler is not None:
             out["config"]["loss_scale"] = {"kind": "dynamic, device-resident (optim.DeviceGradScaler)", "scale": scaler.get_scale(), "skipped_steps": scaler.skipped_steps}
         if ar_ms is not None:

@@ -12,8 +12,35 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_flags_exist():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup", "--batch", "--model", "--dtype", "--inference"):
+    for flag in ("--gpus", "--steps", "--warmup", "--batch", "--model", "--dtype", "--inference", "--dump-outputs"):
         assert flag in out.stdout
+
+
+def test_steps_must_be_positive():
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 2 and "--steps" in out.stderr
+
+
+def test_dump_outputs_fits_64_mb_with_a_fixed_sample(tmp_path):
+    """--dump-outputs at the sizes of the largest default configurations: float32 .npy files under 64 MB in all, `sr` sampled as whole
+    images, and the same sample on every call (two builds' dumps line up element for element)."""
+    import numpy as np
+    import torch
+    import bench
+    g = torch.Generator().manual_seed(0)
+    arrays = {"loss": torch.tensor(0.25), "sr": torch.rand(256, 3, 192, 192, generator=g), "params": torch.rand(43_000_000, generator=g),
+              "grads": torch.rand(1_400_000, generator=g)}
+    shapes = [bench.dump_outputs(str(tmp_path / d), arrays) for d in ("a", "b")]
+    assert shapes[0] == shapes[1] and set(shapes[0]) == set(arrays)
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) < 64e6
+    for name, x in arrays.items():
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, b), name
+    assert np.array_equal(np.load(tmp_path / "a" / "grads.npy"), arrays["grads"].numpy())          # under its share: whole
+    sr = np.load(tmp_path / "a" / "sr.npy")
+    assert sr.shape[1:] == (3, 192, 192) and 1 <= sr.shape[0] < 256
+    full = arrays["sr"].numpy()
+    assert sum(np.array_equal(full[i], sr[-1]) for i in range(256)) == 1                         # a sampled row is a whole image
 
 
 def test_committed_line_has_the_contract_keys():

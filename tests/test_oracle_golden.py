@@ -19,6 +19,16 @@ GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
 MANIFEST = json.load(open(os.path.join(GOLDEN, "manifest.json")))
 
 
+@pytest.fixture(autouse=True)
+def _golden_threads():
+    """The thread count the fixtures were made with (generate_golden.py): torch's CPU convolutions split their reductions by
+    thread count, and the full-depth nets amplify that round-off past their tolerance, so the host's core count must not choose it."""
+    n = torch.get_num_threads()
+    torch.set_num_threads(8)
+    yield
+    torch.set_num_threads(n)
+
+
 def _close(a, b, tol=2e-5):
     a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
     scale = max(1e-6, float(np.abs(b).max()))
