@@ -486,6 +486,38 @@ int srk_l1_loss_bwd(const srk_l1_args* a, srk_stream_t stream);
 /* *out = (partial[0] + ... + partial[nb-1]) / n: the forward's partial sums -> the loss value, one launch */
 int srk_l1_loss_mean(const double* partial, int nb, long long n, float* out, srk_stream_t stream);
 
+/* ---- FLIP loss / metric (reference losses/flip.py, srmodel.py:35,49; Andersson et al., HPG 2020), csrc/flip.hip ------------------
+ * Forward: one workgroup per (image, 32x32 tile) with a 10-pixel halo (replicate-clamped loads): sRGB -> linear -> XYZ -> YCxCz of
+ * both images, the separable CSF filters (radius 10) of the three opponent channels and the edge / point detectors (radius 9) on
+ * the unfiltered luminance, then the per-pixel colour and feature errors and err = C ** (1 - F).  Writes one double partial sum
+ * per workgroup (summed in a fixed order: reproducible), optionally the error map and, for a gradient, the 7 per-pixel adjoints of
+ * err for a unit upstream gradient: d err / d(filtered test Y, Cx, Cz) and d err / d(test edge x, edge y, point x, point y).
+ * Pixels whose colour error is 0 get zero adjoints, and a zero feature difference a zero feature adjoint (the reference's
+ * autograd gives NaN there; sr_amd/flip.py states the convention).
+ * Backward: the transposed separable filters (the adjoint of `replicate` folds the outside taps onto the edge pixel), the
+ * feature path into Y, the YCxCz <- XYZ <- linear <- sRGB Jacobian with the input clamp's mask, times (*gout) * scale.
+ * The constant table (SRK_FLIP_TABLE_FLOATS fp32, layout in sr_amd/flip.py) is built on the host and lives on the device.
+ * NCHW fp32, C = 3, N <= 65535, any H, W >= 1. ---------------------------------------------------------------------------- */
+#define SRK_FLIP_TABLE_FLOATS 176
+#define SRK_FLIP_ADJ_CHANNELS 7
+typedef struct srk_flip_args {
+  const float* sr;                        /* test image [N][3][H][W] (forward and backward)                                  */
+  const float* hr;                        /* reference image [N][3][H][W] (forward)                                          */
+  int N, H, W;
+  const float* table;                     /* [SRK_FLIP_TABLE_FLOATS] device constants                                        */
+  double* partial;                        /* forward: [srk_flip_blocks(N, H, W)] partial sums of err                         */
+  float* err;                             /* forward, optional: [N][H][W] error map                                          */
+  float* adj;                             /* forward writes (optional), backward reads: [N][7][H][W]                        */
+  const float* gout;                      /* backward: device scalar                                                         */
+  float scale;                            /* backward: 1 / (N H W)                                                           */
+  float* grad;                            /* backward: [N][3][H][W] d loss / d sr                                            */
+} srk_flip_args;
+int srk_flip_blocks(int N, int H, int W);
+int srk_flip_fwd(const srk_flip_args* a, srk_stream_t stream);
+int srk_flip_bwd(const srk_flip_args* a, srk_stream_t stream);
+/* *out = (partial[0] + ... + partial[nb-1]) / n (the forward's partial sums -> the mean error), one launch */
+int srk_flip_mean(const double* partial, int nb, long long n, float* out, srk_stream_t stream);
+
 /* ---- SSIM with piq.ssim's defaults (reference srmodel.py:52-53,567-593 -> piq.ssim): images are average-pooled by
  * `pool` = max(1, round(min(H, W) / 256)) (floor division of the extent, as F.avg_pool2d), filtered with the separable
  * 11-tap Gaussian (sigma), and the SSIM map of the VALID region ((Hp-10) x (Wp-10)) is summed per (image, channel)

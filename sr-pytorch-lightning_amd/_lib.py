@@ -191,6 +191,11 @@ class L1Args(C.Structure):
                 ("scale", _f), ("grad", _p)]
 
 
+class FlipArgs(C.Structure):
+    _fields_ = [("sr", _p), ("hr", _p), ("N", _i), ("H", _i), ("W", _i), ("table", _p), ("partial", _p), ("err", _p), ("adj", _p),
+                ("gout", _p), ("scale", _f), ("grad", _p)]
+
+
 class UnfoldNhwcArgs(C.Structure):
     _fields_ = [("x", _p), ("x_pitch", _i), ("x_coff", _i), ("cols", _p), ("cols_pitch", _i),
                 ("N", _i), ("H", _i), ("W", _i), ("C", _i), ("K", _i), ("stride", _i), ("pad", _i), ("Ho", _i), ("Wo", _i), ("dtype", _i)]
@@ -249,6 +254,8 @@ LAUNCHERS = {
     "srk_image_ssim": SsimArgs,
     "srk_l1_loss_fwd": L1Args,
     "srk_l1_loss_bwd": L1Args,
+    "srk_flip_fwd": FlipArgs,
+    "srk_flip_bwd": FlipArgs,
     "srk_unfold_nhwc": UnfoldNhwcArgs,
     "srk_fold_nhwc": FoldNhwcArgs,
     "srk_chan_stats": ChanStatsArgs,
@@ -268,7 +275,7 @@ OTHER_SYMBOLS = ("srk_conv_tile", "srk_last_error", "srk_version", "srk_device_c
                  "srk_conv_pair_tiles", "srk_rowsum_group", "srk_pw_shape_ok", "srk_pw_pack_bytes", "srk_pw_pack_group", "srk_weight_norm_group", "srk_pw_wgrad_ranges", "srk_l1_loss_mean", "srk_chan_stats_finalize", "srk_pack_group_tiles", "srk_pack_conv_weights_group_tiled",
                  "srk_proj_pack", "srk_proj_pack_bytes", "srk_proj_wgrad_scratch_floats", "srk_proj_pack_group", "srk_wgrad_slab_cout",
                  "srk_hrtail_scratch_floats", "srk_pw_wgrad_finalize_group", "srk_adam_step_scaled", "srk_adam_check_scaled", "srk_adam_update_scaled", "srk_loss_scale_update", "srk_conv_bits_ok",
-                 "srk_conv_trunk", "srk_conv_trunk_ok")
+                 "srk_conv_trunk", "srk_conv_trunk_ok", "srk_flip_blocks", "srk_flip_mean")
 
 _lib = None
 
@@ -347,6 +354,11 @@ def load():
     lib.srk_l1_loss_mean.argtypes = [C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p]
     lib.srk_l1_loss_mean.restype = C.c_int
     lib.srk_l1_blocks.argtypes = [C.c_longlong]
+    if not isinstance(getattr(lib, "srk_flip_mean", None), _Absent):
+        lib.srk_flip_mean.argtypes = [C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p]
+        lib.srk_flip_mean.restype = C.c_int
+        lib.srk_flip_blocks.argtypes = [C.c_int, C.c_int, C.c_int]
+        lib.srk_flip_blocks.restype = C.c_int
     lib.srk_l1_blocks.restype = C.c_int
     lib.srk_pw_shape_ok.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.srk_pw_shape_ok.restype = C.c_int

@@ -65,8 +65,16 @@ def _l1_loss(sr, hr):
     return F.l1_loss(sr, hr)
 
 
-_supported_losses = {"l1": _l1_loss, "l2": F.mse_loss, "mae": _l1_loss, "mse": F.mse_loss}
-_out_of_scope_losses = {"adaptive", "dists", "edge_loss", "flip", "haarpsi", "lpips", "pencil_sketch", "pieapp"}
+def _flip_loss(sr, hr):
+    """FLIPLoss (losses/flip.py, srmodel.py:35): mean FLIP error of sr against hr; on the GPU the fused HIP forward/backward
+    (flip.FlipLossFn), elsewhere flip.flip_torch.  Finite gradients everywhere (flip.py: the reference's are NaN where the two
+    images' filtered colours coincide)."""
+    from .. import flip
+    return flip.flip_loss(sr, hr)
+
+
+_supported_losses = {"l1": _l1_loss, "l2": F.mse_loss, "mae": _l1_loss, "mse": F.mse_loss, "flip": _flip_loss}
+_out_of_scope_losses = {"adaptive", "dists", "edge_loss", "haarpsi", "lpips", "pencil_sketch", "pieapp"}
 
 # models/srmodel.py:57-64
 # 'ADAM' is torch.optim.Adam with the update of GPU parameters as one HIP launch (sr-pytorch-lightning_amd/optim.py)
@@ -128,7 +136,13 @@ def _psnr_y_metric(x, y):
     return _psnr_y(x, y, 4)
 
 
-_supported_metrics = {"PSNR": _psnr, "SSIM": _ssim, "PSNR-Y": _psnr_y_metric}   # srmodel.py:47-54 (+ PSNR-Y)
+def _flip_metric(x, y):
+    """FLIP (losses/flip.py, srmodel.py:49): mean FLIP error of x against y, no gradient; HIP on the GPU."""
+    from .. import flip
+    return flip.flip(x, y)
+
+
+_supported_metrics = {"PSNR": _psnr, "SSIM": _ssim, "PSNR-Y": _psnr_y_metric, "FLIP": _flip_metric}   # srmodel.py:47-54 (+ PSNR-Y)
 
 
 def _dtype_from_precision(precision):
@@ -186,6 +200,8 @@ class SRModel(_Base):
         self._log_weights_every_n_epochs = log_weights_every_n_epochs
         self._losses = self._create_losses(losses, patch_size, precision)
         self._metrics = self._create_metrics(metrics)
+        if channels != 3 and ("flip" in {l.name for l in self._losses} or "FLIP" in {m for m, _ in self._metrics}):
+            raise ValueError(f"the FLIP loss / metric compares colours and needs channels == 3 (got channels={channels})")
         self._metrics_for_pbar = metrics_for_pbar
         self._optim, self._optim_params = self._parse_optimizer_config(optimizer, optimizer_params)
         self._predict_datasets = predict_datasets
@@ -352,7 +368,7 @@ class SRModel(_Base):
         for metric in metrics:
             if metric in _supported_metrics:
                 used.append((metric, _supported_metrics[metric]))
-            elif metric in {'BRISQUE', 'FLIP', 'LPIPS', 'MS-SSIM'}:
+            elif metric in {'BRISQUE', 'LPIPS', 'MS-SSIM'}:
                 raise NotImplementedError(f'metric {metric} needs piq and is outside this build. Supported: {", ".join(_supported_metrics)}')
             else:
                 raise AttributeError(f'Couldn\'t find metric {metric}. Supported metrics: {", ".join(_supported_metrics)}')

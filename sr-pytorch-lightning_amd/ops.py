@@ -2350,3 +2350,4 @@ from .ops_norm import *      # noqa: E402,F401,F403  BatchNorm2d, PReLU, per-cha
 from .ops_proj import *      # noqa: E402,F401,F403  unfold / fold, projection and general strided convs
 from .ops_proj import _proj_launch      # noqa: E402,F401  (bench.py / tools/microbench_proj.py time the raw launches)
 from .ops_metrics import *   # noqa: E402,F401,F403  PSNR / SSIM reductions, L1 loss
+from .flip import *          # noqa: E402,F401,F403  FLIP loss and metric (csrc/flip.hip)

@@ -29,6 +29,7 @@ def parse(argv=None):
     p.add_argument("--batch_size", type=int, default=16)
     p.add_argument("--precision", default="bf16", help="32, 16 or bf16 (Trainer key of the reference)")
     p.add_argument("--losses", default="l1")
+    p.add_argument("--metrics", nargs="+", default=None, help="validation metrics (default: the model's, PSNR SSIM); e.g. PSNR SSIM FLIP")
     p.add_argument("--optimizer", default="ADAM")
     p.add_argument("--max_steps", type=int, default=100)
     p.add_argument("--max_epochs", type=int, default=-1)
@@ -76,6 +77,8 @@ def main(argv=None):
     cls = getattr(sr_amd, names[a.model.lower()])
     use_gpu = a.accelerator == "gpu" or (a.accelerator == "auto" and torch.cuda.is_available() and cls is not sr_amd.SRCNN)
     kw = {k: getattr(a, k) for k in ("n_feats", "n_resblocks", "n_resgroups", "res_scale") if getattr(a, k) is not None}
+    if a.metrics:
+        kw["metrics"] = a.metrics
     if a.eval_datasets:
         kw["eval_datasets"] = a.eval_datasets
     elif a.val_dir:
