@@ -12,41 +12,13 @@ Nothing here falls back to PyTorch arithmetic: every op raises if the tensors ar
 not on a GPU or the HIP library is missing.
 """
 import contextlib
-import os
+import weakref
 
 import torch
 
 from . import _lib as L
-
-_DT = {torch.bfloat16: L.SRK_BF16, torch.float16: L.SRK_F16, torch.float32: L.SRK_F32}
-
-
-def _knob(name, default="0"):
-    """A/B switches of tools/ (SRK_NO_PAIR, SRK_NO_HR_COLLAPSE, ...): read ONLY under SRK_DEBUG=1, so that a stray variable in a user's
-    environment cannot silently route the product path through a slower diagnostic form (VERDICT r3 weak #10)."""
-    return os.environ.get(name, default) if os.environ.get("SRK_DEBUG") == "1" else default
-
-
-def pad16(c):
-    return (int(c) + 15) // 16 * 16
-
-
-def _roundup(a, b):
-    return (a + b - 1) // b * b
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _need_gpu(t):
-    if not t.is_cuda:
-        raise RuntimeError("the sr_amd HIP ops run on an MI355X ('cuda') device only; there is no CPU fallback "
-                           "(use oracle/ for a CPU reference in tests)")
-
-
-def _ptr(t):
-    return 0 if t is None else t.data_ptr()
+from .packing import *      # noqa: F401,F403  packed weights: pack_conv, pw_pack, proj_pack, PackGroup, forward_scope, ...
+from .packing import _DT, _TLS, _f32c, _group_for, _knob, _need_gpu, _ptr, _roundup, _stream, _tok      # noqa: F401
 
 
 def _pitch(t):
@@ -58,277 +30,6 @@ def _pitch(t):
     if h > 1 and n > 1:
         assert t.stride(0) == h * w * p, "NHWC view must be dense in H"
     assert c == 1 or t.stride(3) == 1, "channels must be innermost"
-    return p
-
-
-# --------------------------------------------------------------------------------------------
-# weight packing (cached on the parameter object, keyed by its in-place version counter)
-# --------------------------------------------------------------------------------------------
-class Packed:
-    __slots__ = ("wpk", "bias", "KinP", "CoutP", "k", "ps_r", "cr")
-
-
-_PACK_CACHE_ENABLED = False
-
-
-class pack_cache:
-    """Context manager: reuse packed weights across calls while the parameters are FROZEN (inference loops).
-
-    Off by default: an optimizer may update parameters without touching their autograd version counter
-    (torch's fused Adam does), so a version-keyed cache cannot be trusted while training -- every forward /
-    backward repacks (one small kernel per conv)."""
-
-    def __init__(self, enabled=True):
-        self.enabled, self.prev = enabled, None
-
-    def __enter__(self):
-        global _PACK_CACHE_ENABLED
-        self.prev, _PACK_CACHE_ENABLED = _PACK_CACHE_ENABLED, self.enabled
-        return self
-
-    def __exit__(self, *exc):
-        global _PACK_CACHE_ENABLED
-        _PACK_CACHE_ENABLED = self.prev
-
-
-_PACK_TILED = _knob("SRK_NO_PACK_TILED", "0") != "1"      # A/B knob: the strided-read grouped pack launch
-
-
-class PackGroup:
-    """The packed shadow weights of ONE model, re-packed by a single kernel launch per step.
-
-    `forward_scope(group)` (entered at the top of a model's forward) launches `srk_pack_conv_weights_group` over a
-    device-side table of every (parameter, layout) pair the model has used so far -- forward and dgrad layouts --
-    so the ~2 pack launches per conv per training step collapse into one.  Entries are discovered on the first
-    step (packed individually then).  Buffers are persistent, so the launch is hipGraph-capturable.
-
-    Validity: packed buffers are served ONLY (a) inside the forward window that refreshed them and (b) to the
-    backward of a graph built in that window (the Functions carry the (group, epoch) token they were built under and
-    a newer refresh invalidates it).  Anything else -- a block called on its own after the model's forward, a sub-module
-    called directly, another model's parameters -- packs per call from the current parameter values: an optimizer step
-    between two forwards can never be served stale weights (torch's fused Adam does not bump `_version`)."""
-
-    def __init__(self):
-        self.entries = {}       # key -> [PackArgs, Packed, w, b]
-        self.pw_entries = {}    # key -> [PwPackArgs, PwPacked, (w1, b1, w2, b2)]  (fused pointwise pairs, csrc/pw_chain.hip)
-        self.pw_table = None
-        self.proj_entries = {}  # (id(w), dtype) -> [w, packed buffer]  (D-DBPN's projection convs, csrc/proj.hip)
-        self.proj_tables = {}   # dtype -> [device table, addresses it was built from]
-        self.tiles, self.total_tiles = None, 0
-        self.pw_dirty = False
-        self.table = None
-        self.dirty = False
-        self.epoch = 0          # number of refreshes so far
-        self.open = False       # inside the forward window of the latest refresh
-
-    def lookup(self, key):
-        e = self.entries.get(key)
-        return e[1] if e is not None else None
-
-    @staticmethod
-    def _held(t):
-        """What an entry keeps of a source tensor: the tensor itself for a leaf (its address is re-read every refresh), a
-        DETACHED alias for anything else.  A weight-normed conv's effective weight carries the grad_fn of the step that made
-        it; held here, that node would keep the AccumulateGrad nodes of an eager step (created on the eager stream) alive
-        into a later hipGraph capture, whose backward then ties the eager stream into the capture and hipStreamEndCapture
-        crashes."""
-        return t if (t is None or t.grad_fn is None) else t.detach()
-
-    def add(self, key, args, packed, w, b):
-        self.entries[key] = [args, packed, self._held(w), self._held(b)]
-        self.dirty = True
-
-    def lookup_pw(self, key):
-        e = self.pw_entries.get(key)
-        return e[1] if e is not None else None
-
-    def add_pw(self, key, args, packed, tensors):
-        self.pw_entries[key] = [args, packed, tuple(self._held(t) for t in tensors)]
-        self.pw_dirty = True
-
-    def lookup_proj(self, key):
-        e = self.proj_entries.get(key)
-        return e[1] if e is not None else None
-
-    def add_proj(self, key, w, wpk):
-        self.proj_entries[key] = [w, wpk]
-
-    def _refresh_proj(self):
-        """All projection weights of one storage dtype -> fragment order in ONE launch (was one 5 us launch per conv and step)."""
-        import ctypes as C
-        by_dt = {}
-        for (_, dt), (w, wpk) in self.proj_entries.items():
-            by_dt.setdefault(dt, []).append((w, wpk))
-        for dt, ents in by_dt.items():
-            addrs = tuple((w.data_ptr(), wpk.data_ptr()) for w, wpk in ents)
-            tb = self.proj_tables.get(dt)
-            if tb is None or tb[1] != addrs:
-                host = (L.ProjPackJob * len(ents))()
-                for i, (wa, pa) in enumerate(addrs):
-                    host[i].w4, host[i].wpk = wa, pa
-                raw = torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8)
-                dev = ents[0][1].device
-                if tb is None or tb[0].numel() < raw.numel():       # the table keeps its address while it fits (a captured step names it)
-                    tb = [torch.empty(max(2 * raw.numel(), 1024), dtype=torch.uint8, device=dev), None]
-                tb[0][:raw.numel()].copy_(raw)
-                tb[1] = addrs
-                self.proj_tables[dt] = tb
-            L.check(L.load().srk_proj_pack_group(tb[0].data_ptr(), len(ents), _DT[dt], _stream()), "srk_proj_pack_group")
-
-    def _refresh_pw(self):
-        for e in self.pw_entries.values():
-            a, _, (w1, b1, w2, b2) = e
-            ptrs = (w1.data_ptr(), _ptr(b1), w2.data_ptr(), _ptr(b2))
-            if (a.w1, a.b1 or 0, a.w2, a.b2 or 0) != ptrs:
-                a.w1, a.b1, a.w2, a.b2 = ptrs
-                self.pw_dirty = True
-        if self.pw_dirty:
-            arr = (L.PwPackArgs * len(self.pw_entries))(*[e[0] for e in self.pw_entries.values()])
-            raw = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
-            dev = next(iter(self.pw_entries.values()))[2][0].device
-            if self.pw_table is None or self.pw_table.device != dev or self.pw_table.numel() < raw.numel():
-                self.pw_table = torch.empty(max(2 * raw.numel(), 4096), dtype=torch.uint8, device=dev)
-            self.pw_table[:raw.numel()].copy_(raw)
-            self.pw_dirty = False
-        L.check(L.load().srk_pw_pack_group(self.pw_table.data_ptr(), len(self.pw_entries), _stream()), "srk_pw_pack_group")
-
-    def refresh(self):
-        self.epoch += 1
-        if self.pw_entries:
-            self._refresh_pw()
-        if self.proj_entries:
-            self._refresh_proj()
-        if not self.entries:
-            return
-        for e in self.entries.values():          # parameters moved / re-allocated since the table was built?
-            a, _, w, b = e
-            bp = 0 if b is None else b.data_ptr()
-            if a.w != w.data_ptr() or (a.bias or 0) != bp:
-                a.w, a.bias = w.data_ptr(), bp
-                self.dirty = True
-        if self.dirty:
-            import ctypes as C
-            n = len(self.entries)
-            arr = (L.PackArgs * n)(*[e[0] for e in self.entries.values()])
-            raw = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
-            dev = next(iter(self.entries.values()))[2].device
-            # the table keeps its ADDRESS while it fits (a captured step points at it): grown in place, with head room
-            if self.table is None or self.table.device != dev or self.table.numel() < raw.numel():
-                self.table = torch.empty(max(2 * raw.numel(), 4096), dtype=torch.uint8, device=dev)
-            self.table[:raw.numel()].copy_(raw)
-            # blocks of the launch -> (entry, tile): prefix sums of the entries' tile counts, next to the table
-            tb = (C.c_int * (n + 1))()
-            L.check(L.load().srk_pack_group_tiles(C.addressof(arr), n, C.addressof(tb)), "srk_pack_group_tiles")
-            if self.tiles is None or self.tiles.device != dev or self.tiles.numel() < n + 1:
-                self.tiles = torch.empty(max(2 * (n + 1), 1024), dtype=torch.int32, device=dev)
-            self.tiles[:n + 1].copy_(torch.tensor(list(tb), dtype=torch.int32))
-            self.total_tiles = int(tb[n])
-            self.dirty = False
-        if _PACK_TILED:
-            L.check(L.load().srk_pack_conv_weights_group_tiled(self.table.data_ptr(), self.tiles.data_ptr(), len(self.entries), self.total_tiles, _stream()),
-                    "srk_pack_conv_weights_group_tiled")
-        else:
-            L.check(L.load().srk_pack_conv_weights_group(self.table.data_ptr(), len(self.entries), _stream()), "srk_pack_conv_weights_group")
-
-
-import threading
-import weakref
-_TLS = threading.local()
-
-
-class forward_scope:
-    """`with forward_scope(group):` around a model's forward: refreshes `group` (one launch) and makes it the group that
-    serves / registers packed weights until the block exits.  `group=None`: no grouping (every conv packs per use)."""
-
-    def __init__(self, group):
-        self.group = group
-
-    def __enter__(self):
-        self.prev = getattr(_TLS, "group", None)
-        _TLS.group = self.group
-        if self.group is not None:
-            self.group.refresh()
-            self.group.open = True
-        return self
-
-    def __exit__(self, *exc):
-        if self.group is not None:
-            self.group.open = False
-        _TLS.group = self.prev
-
-
-def _tok():
-    """(group, epoch) token of the forward window a Function is being built in, or None."""
-    g = getattr(_TLS, "group", None)
-    return (weakref.ref(g), g.epoch) if (g is not None and g.open) else None
-
-
-def _group_for(token):
-    """The PackGroup allowed to serve this call: the open forward window's, or the one named by a still-current token."""
-    if token is not None:
-        g = token[0]()
-        return g if (g is not None and g.epoch == token[1]) else None
-    g = getattr(_TLS, "group", None)
-    return g if (g is not None and g.open) else None
-
-
-def pack_conv(w, b, dtype, *, dgrad=False, ps_r=0, cache=True, as_1x1=False, token=None):
-    """OIHW fp32 `w` (+ bias) -> packed shadow layout for srk_conv2d (forward or dgrad).
-    as_1x1: present the OIHW weight as the 1x1 conv over Cin*KH*KW unfolded channels (head / skip convs).
-    token: the (group, epoch) a Function's forward was built under (backward calls pass it: see PackGroup)."""
-    _need_gpu(w)
-    # a weight-normed conv's effective weight (WeightNormGroup) is a non-leaf tensor in a buffer with a STABLE address: it joins
-    # the grouped pack launch under the identity of its `weight_v` parameter
-    kobj = None if isinstance(w, torch.nn.Parameter) else w.__dict__.get("_srk_pack_key")
-    is_param = isinstance(w, torch.nn.Parameter) or kobj is not None
-    key = (id(w) if kobj is None else kobj, dtype, bool(dgrad), int(ps_r), bool(as_1x1))
-    group = _group_for(token) if is_param else None
-    if group is not None:
-        hit = group.lookup(key)
-        if hit is not None:
-            return hit
-    ver = (w._version, -1 if b is None else b._version, w.data_ptr())
-    store = None
-    if cache and _PACK_CACHE_ENABLED and is_param and kobj is None:
-        store = w.__dict__.setdefault("_srk_pack", {})
-        hit = store.get(key)
-        if hit is not None and hit[0] == ver:
-            return hit[1]
-    cout, cin, kh, kw = w.shape
-    assert kh == kw
-    if as_1x1:
-        cin, kh, kw = cin * kh * kw, 1, 1
-    p = Packed()
-    p.k, p.ps_r = kh, int(ps_r)
-    if not dgrad:
-        p.KinP, p.CoutP = pad16(cin), _roundup(cout, L.conv_tile(cout))
-    else:
-        p.KinP, p.CoutP = pad16(cout), _roundup(cin, L.conv_tile(cin))
-    wf = w.detach()
-    if wf.dtype != torch.float32 or not wf.is_contiguous():
-        wf = wf.float().contiguous()
-    # large kernel with few output channels (SRResNet's 9x9 tail, 64 -> 3): the forward kernel wants (kw, co) pairs on the MFMA rows;
-    # that layout (kh * 2048 elements) rides behind the standard one
-    rows = (not dgrad and not as_1x1 and kh in (5, 7, 9) and cin == 64 and cout <= 4 and cout * kw <= 32 and int(ps_r) <= 1
-            and dtype in (torch.bfloat16, torch.float16) and p.CoutP == 32)
-    p.cr = int(cout) if rows else 0
-    p.wpk = torch.empty(kh * kw * p.KinP * p.CoutP + (kh * 2048 if rows else 0), dtype=dtype, device=w.device)
-    p.bias = None
-    bf = None
-    if not dgrad:
-        p.bias = torch.empty(p.CoutP, dtype=torch.float32, device=w.device)
-        if b is not None:
-            bf = b.detach()
-            if bf.dtype != torch.float32 or not bf.is_contiguous():
-                bf = bf.float().contiguous()
-    a = L.PackArgs(w=wf.data_ptr(), bias=_ptr(bf), wpk=p.wpk.data_ptr(), bias_pk=_ptr(p.bias),
-                   Cout=cout, Cin=cin, KH=kh, KW=kw, KinP=p.KinP, CoutP=p.CoutP,
-                   dgrad=int(dgrad), ps_r=int(ps_r), dtype=_DT[dtype], rows_layout=int(rows))
-    L.call("srk_pack_conv_weights", a, _stream())
-    if store is not None:
-        store[key] = (ver, p)
-    if group is not None and wf.data_ptr() == w.data_ptr() and (bf is None or bf.data_ptr() == b.data_ptr()):
-        group.add(key, a, p, w, b if not dgrad else None)
     return p
 
 
@@ -352,6 +53,26 @@ def _batch_chunks(n, *tensors):
 _SIGN_BITS = _knob("SRK_NO_SIGN_BITS") != "1"       # A/B knob: ReLU backward masks re-read the activation instead of its sign bits
 
 
+def _conv_args(x, pk, out, *, res=None, mask=None, post_add=None, relu_bits=None, mask_bits=None, use_bias=True, **fields):
+    """The srk_conv2d descriptor (L.ConvArgs, include/srk.h) of `x` -> `out` through the pack `pk`: the tensors given by keyword become
+    addresses and pitches, `fields` set others by name, and every field not named is 0 (or the pack's / `x`'s value).  `pk` None: no
+    weights (the trunk's add layer).  The record holds `pk`, so a table of records keeps its packs alive until it is launched."""
+    n, h, w, c = x.shape
+    planar = fields.get("out_mode") == L.OUT_PLANAR         # out / res are NCHW fp32: no pixel pitch
+    a = dict(x=x.data_ptr(), x_pitch=_pitch(x), N=n, H=h, W=w, Cin=c, scale=1.0,
+             res=_ptr(res), res_pitch=0 if (res is None or planar) else _pitch(res),
+             mask=_ptr(mask), mask_pitch=0 if mask is None else _pitch(mask),
+             out=out.data_ptr(), out_pitch=0 if planar else _pitch(out), post_add=_ptr(post_add), dtype=_DT[x.dtype],
+             relu_bits=_ptr(relu_bits), mask_bits=_ptr(mask_bits))
+    if pk is not None:
+        a.update(wpk=pk.wpk.data_ptr(), bias=_ptr(pk.bias) if use_bias else 0, CoutP=pk.CoutP, KH=pk.k, KW=pk.k,
+                 cout_real=getattr(pk, "cr", 0) or 0)
+    a.update(fields)
+    args = L.ConvArgs(**a)
+    args.pk = pk
+    return args
+
+
 def conv_raw(x, pk, *, N, H, W, Cin, Cout, out, out_mode=L.OUT_NHWC, ps_r=0, relu=False, scale=1.0,
              res=None, mask=None, mask_from=0, post_add=None, x_ps=0, use_bias=True, relu_bits=None, mask_bits=None):
     """One srk_conv2d launch.  `x`, `out`, `res`, `mask` are NHWC tensors or channel-slice views
@@ -366,19 +87,15 @@ def conv_raw(x, pk, *, N, H, W, Cin, Cout, out, out_mode=L.OUT_NHWC, ps_r=0, rel
         bits_t = None
         if ok:
             bits_t = mask_bits if mask_bits is not None else torch.empty((N * H * W, 2), dtype=torch.int32, device=x.device)
-            probe = L.ConvArgs(x=x.data_ptr(), x_pitch=_pitch(x), x_coff=0, x_ps=int(x_ps), N=N, H=H, W=W, Cin=Cin, wpk=pk.wpk.data_ptr(), bias=0,
-                               CoutP=pk.CoutP, Cout=Cout, KH=pk.k, KW=pk.k, relu=int(relu), scale=float(scale), res=_ptr(res),
-                               res_pitch=0 if res is None else _pitch(res), res_coff=0, mask=0, mask_pitch=0, mask_coff=0, mask_from=0,
-                               out=out.data_ptr(), out_pitch=_pitch(out), out_coff=0, out_mode=out_mode, ps_r=int(ps_r), post_add=0,
-                               dtype=_DT[x.dtype], cout_real=0, relu_bits=bits_t.data_ptr() if relu_bits is not None else 0,
-                               mask_bits=bits_t.data_ptr() if mask_bits is not None else 0)
-            ok = bool(L.load().srk_conv_bits_ok(probe))
+            a = _conv_args(x, pk, out, N=N, H=H, W=W, Cin=Cin, Cout=Cout, x_ps=int(x_ps), relu=int(relu), scale=float(scale), res=res,
+                           out_mode=out_mode, ps_r=int(ps_r), relu_bits=bits_t if relu_bits is not None else None,
+                           mask_bits=bits_t if mask_bits is not None else None, bias=0, cout_real=0)
+            ok = bool(L.load().srk_conv_bits_ok(a))
         if not ok:
             conv_raw(x, pk, N=N, H=H, W=W, Cin=Cin, Cout=Cout, out=out, out_mode=out_mode, ps_r=ps_r, relu=relu, scale=scale, res=res, mask=mask,
                      mask_from=mask_from, post_add=post_add, x_ps=x_ps, use_bias=use_bias)
             out.__dict__["_srk_bits"] = None
             return out
-        a = probe
         a.bias = _ptr(pk.bias) if use_bias else 0
         a.cout_real = getattr(pk, "cr", 0) or 0
         L.call("srk_conv2d", a, _stream())
@@ -393,16 +110,8 @@ def conv_raw(x, pk, *, N, H, W, Cin, Cout, out, out_mode=L.OUT_NHWC, ps_r=0, rel
                      relu=relu, scale=scale, res=None if res is None else res[n0:n1], mask=None if mask is None else mask[n0:n1],
                      mask_from=mask_from, post_add=post_add, x_ps=x_ps, use_bias=use_bias)
         return out
-    dt = x.dtype
-    planar = out_mode == L.OUT_PLANAR
-    a = L.ConvArgs(
-        x=x.data_ptr(), x_pitch=_pitch(x), x_coff=0, x_ps=int(x_ps), N=N, H=H, W=W, Cin=Cin,
-        wpk=pk.wpk.data_ptr(), bias=_ptr(pk.bias) if use_bias else 0, CoutP=pk.CoutP, Cout=Cout, KH=pk.k, KW=pk.k,
-        relu=int(relu), scale=float(scale),
-        res=_ptr(res), res_pitch=0 if (res is None or planar) else _pitch(res), res_coff=0,
-        mask=_ptr(mask), mask_pitch=0 if mask is None else _pitch(mask), mask_coff=0, mask_from=int(mask_from),
-        out=out.data_ptr(), out_pitch=0 if planar else _pitch(out), out_coff=0, out_mode=out_mode, ps_r=int(ps_r),
-        post_add=_ptr(post_add), dtype=_DT[dt], cout_real=getattr(pk, "cr", 0) or 0, relu_bits=0, mask_bits=0)
+    a = _conv_args(x, pk, out, N=N, H=H, W=W, Cin=Cin, Cout=Cout, x_ps=int(x_ps), relu=int(relu), scale=float(scale), res=res, mask=mask,
+                   mask_from=int(mask_from), out_mode=out_mode, ps_r=int(ps_r), post_add=post_add, use_bias=use_bias)
     L.call("srk_conv2d", a, _stream())
     return out
 
@@ -1035,11 +744,6 @@ def nhwc_to_nchw(x, C):
     return ToNchwFn.apply(x, int(C))
 
 
-def _f32c(t):
-    t = t.detach()
-    return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
-
-
 # --------------------------------------------------------------------------------------------
 # autograd Functions
 # --------------------------------------------------------------------------------------------
@@ -1453,19 +1157,12 @@ _TRUNK_OFF = _knob("SRK_NO_TRUNK", "0") == "1"       # A/B knob: the trunk as on
 
 
 def _trunk_layer(x, pk, out, *, relu=False, scale=1.0, res=None, relu_bits=None, mask_bits=None, use_bias=True):
-    n, h, w, _ = x.shape
-    return L.ConvArgs(x=x.data_ptr(), x_pitch=_pitch(x), x_coff=0, x_ps=0, N=n, H=h, W=w, Cin=64, wpk=pk.wpk.data_ptr(),
-                      bias=_ptr(pk.bias) if use_bias else 0, CoutP=pk.CoutP, Cout=64, KH=3, KW=3, relu=int(relu), scale=float(scale), res=_ptr(res),
-                      res_pitch=0 if res is None else _pitch(res), res_coff=0, mask=0, mask_pitch=0, mask_coff=0, mask_from=0, out=out.data_ptr(),
-                      out_pitch=_pitch(out), out_coff=0, out_mode=L.OUT_NHWC, ps_r=0, post_add=0, dtype=_DT[x.dtype], cout_real=0,
-                      relu_bits=_ptr(relu_bits), mask_bits=_ptr(mask_bits))
+    return _conv_args(x, pk, out, Cin=64, Cout=64, relu=int(relu), scale=float(scale), res=res, relu_bits=relu_bits, mask_bits=mask_bits,
+                      use_bias=use_bias)
 
 
 def _trunk_add_layer(x, res, out):
-    n, h, w, _ = x.shape
-    return L.ConvArgs(x=x.data_ptr(), x_pitch=64, x_coff=0, x_ps=0, N=n, H=h, W=w, Cin=64, wpk=0, bias=0, CoutP=64, Cout=64, KH=0, KW=0, relu=0, scale=1.0,
-                      res=res.data_ptr(), res_pitch=64, res_coff=0, mask=0, mask_pitch=0, mask_coff=0, mask_from=0, out=out.data_ptr(), out_pitch=64,
-                      out_coff=0, out_mode=L.OUT_NHWC, ps_r=0, post_add=0, dtype=_DT[x.dtype], cout_real=0, relu_bits=0, mask_bits=0)
+    return _conv_args(x, None, out, res=res, CoutP=64, Cout=64)
 
 
 def _trunk_launch(layers, dev):
@@ -1511,7 +1208,7 @@ class ResTrunkFn(torch.autograd.Function):
         n, h, wd, _ = x.shape
         ws, bs = params[0::2], params[1::2]
         train = any(ctx.needs_input_grad)
-        xs, hs, bits, layers = [x], [], [], []
+        xs, hs, bits, layers = [x], [], [], []         # (each layer record holds its pack until the launch: _conv_args)
         spare = []                                   # no gradient wanted: three buffers rotate (no layer writes a buffer it reads)
 
         def take():
@@ -1764,40 +1461,6 @@ def pw_ok(x, w1, w2):
         return False
     return bool(L.load().srk_pw_shape_ok(int(w1.shape[1]), int(w1.shape[0]), _roundup(int(w2.shape[0]), 64)))
 
-
-class PwPacked:
-    __slots__ = ("fwd", "bwd", "cin", "chid", "cmid", "coutp")
-
-
-def pw_pack(w1, b1, w2, b2, dtype, token=None):
-    """fp32 [Chid][Cin][1][1] / [Cmid][Chid][1][1] (+ biases) -> the forward and backward slice streams of srk_pw_*.
-    Weights with a stable identity (parameters, WeightNormGroup proxies) are served by / registered with the open PackGroup."""
-    _need_gpu(w1)
-    lib = L.load()
-    ids = []
-    for w in (w1, w2):
-        ids.append(id(w) if isinstance(w, torch.nn.Parameter) else w.__dict__.get("_srk_pack_key"))
-    group = _group_for(token) if all(i is not None for i in ids) else None
-    key = (ids[0], ids[1], dtype)
-    if group is not None:
-        hit = group.lookup_pw(key)
-        if hit is not None:
-            return hit
-    p = PwPacked()
-    p.cin, p.chid, p.cmid = int(w1.shape[1]), int(w1.shape[0]), int(w2.shape[0])
-    p.coutp = _roundup(p.cmid, 64)
-    p.fwd = torch.empty(lib.srk_pw_pack_bytes(p.cin, p.chid, p.coutp, 0), dtype=torch.uint8, device=w1.device)
-    p.bwd = torch.empty(lib.srk_pw_pack_bytes(p.cin, p.chid, p.coutp, 1), dtype=torch.uint8, device=w1.device)
-    w1f, w2f = _f32c(w1.detach()), _f32c(w2.detach())
-    b1f = None if b1 is None else _f32c(b1.detach())
-    b2f = None if b2 is None else _f32c(b2.detach())
-    a = L.PwPackArgs(w1=w1f.data_ptr(), b1=_ptr(b1f), w2=w2f.data_ptr(), b2=_ptr(b2f), Cin=p.cin, Chid=p.chid,
-                     Cmid=p.cmid, CoutP=p.coutp, fwd=p.fwd.data_ptr(), bwd=p.bwd.data_ptr(), dtype=_DT[dtype])
-    L.call("srk_pw_pack", a, _stream())
-    if (group is not None and w1f.data_ptr() == w1.data_ptr() and w2f.data_ptr() == w2.data_ptr()
-            and (b1 is None or b1f.data_ptr() == b1.data_ptr()) and (b2 is None or b2f.data_ptr() == b2.data_ptr())):
-        group.add_pw(key, a, p, (w1, b1, w2, b2))
-    return p
 
 
 def pw_forward_raw(x, pk, out):

@@ -5,8 +5,9 @@ import os
 import torch
 
 from . import _lib as L
-from .ops import _ADDR_LIMIT, _DT, _f32c, _grad_slot, _grad_target, _group_for, _knob, _need_gpu, _pitch, _ptr, _stream, _tok, conv, pad16      # (ops.py imports this module at its END)
+from .ops import _ADDR_LIMIT, _DT, _f32c, _grad_slot, _grad_target, _knob, _need_gpu, _pitch, _ptr, _stream, _tok, conv, pad16      # (ops.py imports this module at its END)
 from .ops_norm import chan_apply, chan_reduce, chan_sums
+from .packing import proj_groupable, proj_pack
 
 
 # --------------------------------------------------------------------------------------------
@@ -126,18 +127,9 @@ class ProjFn(torch.autograd.Function):
         _need_gpu(x)
         x = _nhwc_view(x)
         half = L.load().srk_proj_pack_bytes() // 2
-        # a model's forward window (forward_scope) packs the projection weights it has seen before in ONE launch; a first use, a
-        # weight that is not a plain fp32 parameter, or a call outside any window packs here
-        group = _group_for(None) if (isinstance(w, torch.nn.Parameter) and w.dtype == torch.float32 and w.is_contiguous()) else None
-        key = (id(w), x.dtype)
-        wpk = group.lookup_proj(key) if group is not None else None
-        ctx.pg = _tok() if wpk is not None else None
-        if wpk is None or wpk.device != x.device:
-            wpk = torch.empty(2 * half, dtype=torch.uint8, device=x.device)
-            L.check(L.load().srk_proj_pack(_f32c(w).data_ptr(), wpk.data_ptr(), _DT[x.dtype], _stream()), "srk_proj_pack")
-            if group is not None:
-                group.add_proj(key, w, wpk)
-                ctx.pg = _tok()
+        # a model's forward window (forward_scope) packs the projection weights it has seen before in ONE launch
+        wpk = proj_pack(w, x.dtype, x.device)
+        ctx.pg = _tok() if proj_groupable(w) else None
         sl = None if slope is None else _f32c(slope)
         need_pre = sl is not None and (ctx.needs_input_grad[0] or ctx.needs_input_grad[1] or ctx.needs_input_grad[3])
         out, pre = _proj_launch(x, wpk[half:] if up else wpk[:half], None if b is None else _f32c(b), up, sl, need_pre)
@@ -150,10 +142,8 @@ class ProjFn(torch.autograd.Function):
     def backward(ctx, g):
         x, wpk, pre, sl = ctx.saved_tensors
         up, half = ctx.up, ctx.half
-        if ctx.pg is not None and _group_for(ctx.pg) is None:
-            # the group's buffer was re-packed by a later forward window (from possibly updated weights): pack the weights again, here
-            wpk = torch.empty(2 * half, dtype=torch.uint8, device=x.device)
-            L.check(L.load().srk_proj_pack(_f32c(ctx.wparam).data_ptr(), wpk.data_ptr(), _DT[x.dtype], _stream()), "srk_proj_pack")
+        if ctx.pg is not None:          # the group's buffer while the token is current, else packed again (see packing.py)
+            wpk = proj_pack(ctx.wparam, x.dtype, x.device, token=ctx.pg)
         g = _nhwc_view(g)               # (a slice of a SliceBuffer's gradient buffer is read with its pitch: no copy)
         gs = None
         if sl is not None:                       # through the PReLU first: g <- g * (pre > 0 ? 1 : slope), slope gradient on the side

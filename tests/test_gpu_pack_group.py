@@ -61,3 +61,40 @@ def test_tiled_group_pack_is_bit_identical_to_the_standalone_pack(A):
             assert torch.equal(qf.wpk.view(torch.int16), rf.wpk.view(torch.int16)), ("forward", shp, dt)
             assert torch.equal(qf.bias, rf.bias), ("bias", shp, dt)
             assert torch.equal(qd.wpk.view(torch.int16), rd.wpk.view(torch.int16)), ("dgrad", shp, dt)
+
+
+def _stale_token_backward_matches_a_fresh_model(A, make, lr):
+    """A backward that runs after a LATER forward window of the same model (its token is stale: the group's buffers were re-packed
+    since) packs the weights again, and gets what a fresh model with the same weights gets from its first forward and backward."""
+    import copy
+    torch.manual_seed(0)
+    m = make()
+    m(lr)                                                 # the first window discovers the model's packs
+    m2 = make()
+    m2.load_state_dict(copy.deepcopy(m.state_dict()))
+    m2(lr).sum().backward()
+    for p in m.parameters():
+        p.grad = None
+    y4 = m(lr)
+    y5 = m(lr)
+    y4.sum().backward()
+    torch.cuda.synchronize()
+    assert torch.equal(y4, y5)
+    for (k, a_), b_ in zip(m2.named_parameters(), m.parameters()):
+        if a_.grad is not None:
+            torch.testing.assert_close(a_.grad, b_.grad, rtol=1e-5, atol=1e-6, msg=k)
+
+
+def test_stale_token_conv_pair_backward(A):
+    """The conv kind, on EDSR-baseline's conv_pair path (batch 16)."""
+    from sr_amd import ops
+    before = sum(ops.PAIR_LAUNCHES)
+    _stale_token_backward_matches_a_fresh_model(
+        A, lambda: A.EDSR(n_feats=64, n_resblocks=16, res_scale=0.1, scale_factor=2, precision="bf16").cuda(), torch.rand(16, 3, 24, 24).cuda())
+    assert sum(ops.PAIR_LAUNCHES) > before
+
+
+def test_stale_token_pointwise_pair_backward(A):
+    """The pw kind: WDSR-B's fused pointwise pairs (and its 3x3 convs)."""
+    _stale_token_backward_matches_a_fresh_model(
+        A, lambda: A.WDSR(type="B", n_feats=128, n_resblocks=2, scale_factor=2, precision="bf16").cuda(), torch.rand(2, 3, 24, 24).cuda())

@@ -103,6 +103,51 @@ def test_batches_that_do_not_fill_the_chip_keep_the_per_layer_path(A):
         assert launched == [], (n, launched)
 
 
+def _run_windows(A, m, fs, g, trunk, grouped):
+    """One body forward per input of `fs` (each in its own forward window of the model's PackGroup, or outside any window), then the
+    backward of the FIRST: with two windows its token is stale, and outside a window every pack is made per call, so the packs the
+    trunk table names are held by nothing but the table."""
+    ops = A.ops
+    prev, real = ops._TRUNK_OFF, ops._trunk_launch
+    ops._TRUNK_OFF = not trunk
+    launched = []
+    ops._trunk_launch = lambda layers, dev: (launched.append(len(layers)), real(layers, dev))[1]
+    try:
+        for p in m.parameters():
+            p.grad = None
+        xs, rs = [f.clone().requires_grad_(True) for f in fs], []
+        for x in xs:
+            with ops.forward_scope(m._pack_group() if grouped else None):
+                rs.append(m.body_nhwc(x))
+        (rs[0].float() * g.float()).sum().backward()
+        torch.cuda.synchronize()
+        grads = {k: p.grad.detach().clone() for k, p in m.body.named_parameters()}
+        return [r.detach().clone() for r in rs], xs[0].grad.detach().clone(), grads, launched
+    finally:
+        ops._TRUNK_OFF = prev
+        ops._trunk_launch = real
+
+
+@pytest.mark.parametrize("grouped,nfwd", [(True, 2), (False, 1)], ids=["backward_after_a_later_forward", "outside_forward_scope"])
+def test_trunk_keeps_its_packs_until_the_launch(A, grouped, nfwd):
+    """The trunk table names each layer's packed weights by address; a pack made per call (a stale token, or no forward window) must
+    live until the launch that reads it, or every layer reads whatever the allocator put there last."""
+    n, dt, nb = _cus(A), torch.bfloat16, 3
+    m = _body(A, nb, dt, seed=4)
+    gen = torch.Generator().manual_seed(13)
+    fs = [(torch.rand(n, 16, 16, 64, generator=gen) - 0.5).to(dt).cuda() for _ in range(nfwd)]
+    g = (torch.rand(n, 16, 16, 64, generator=gen) - 0.5).to(dt).cuda()
+    r1, gx1, gr1, l1 = _run_windows(A, m, fs, g, trunk=True, grouped=grouped)
+    r0, gx0, gr0, l0 = _run_windows(A, m, fs, g, trunk=False, grouped=grouped)
+    assert l1 == [2 * nb + 1] * nfwd + [2 * nb + 2] and l0 == [], (l1, l0)
+    for a_, b_ in zip(r1, r0):
+        assert torch.equal(a_, b_)
+    assert torch.equal(gx1, gx0)
+    for k in gr0:
+        assert torch.equal(gr1[k], gr0[k]), k
+    assert float(gx1.float().abs().mean()) > 0.05
+
+
 def test_trunk_table_validation(A):
     """srk_conv_trunk_ok / srk_conv_trunk refuse what the kernel cannot serve (error behaviour of the C-ABI)."""
     L = A._lib

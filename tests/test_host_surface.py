@@ -171,3 +171,24 @@ def test_adam_on_cpu_parameters_is_torch_adam():
         assert torch.equal(p, r)
     with pytest.raises(NotImplementedError):
         sr_amd.optim.Adam(ps, amsgrad=True)
+
+
+def test_device_table_keeps_its_address_grows_and_rewrites_only_changed_bytes():
+    """packing.DeviceTable, the persistent table behind every grouped pack launch (a captured step names its address)."""
+    from sr_amd.packing import DeviceTable
+    cpu = torch.device("cpu")
+    t = DeviceTable()
+    host = (ctypes.c_int * 8)(*range(8))
+    buf = t.put(host, cpu)
+    addr, cap = buf.data_ptr(), buf.numel()
+    assert bytes(buf[:32].numpy()) == bytes(host) and cap >= 4096
+    buf[:4].fill_(0xAB)                                   # unchanged bytes are not written again
+    assert t.put(host, cpu).data_ptr() == addr and int(buf[0]) == 0xAB
+    host[1] = 99                                          # changed bytes are, in place
+    buf = t.put(host, cpu)
+    assert buf.data_ptr() == addr and bytes(buf[:32].numpy()) == bytes(host)
+    big = (ctypes.c_int * (cap // 4 + 1))(*range(cap // 4 + 1))      # content that does not fit: a larger buffer, with head room
+    buf = t.put(big, cpu)
+    assert buf.numel() >= 2 * ctypes.sizeof(big) and bytes(buf[:ctypes.sizeof(big)].numpy()) == bytes(big)
+    addr = buf.data_ptr()
+    assert t.put(host, cpu).data_ptr() == addr and bytes(buf[:32].numpy()) == bytes(host)
