@@ -1122,16 +1122,6 @@ __global__ __launch_bounds__(256) void pw_wgrad_finalize_kernel(const srk_pw_wgr
   pw_fin_item(a, NR, RI, R2, (long long)blockIdx.x * 256 + threadIdx.x);
 }
 
-// The finalize steps of SEVERAL pointwise pairs in one launch (round 5; VERDICT r4 weak #4: WDSR-B's 16 blocks issued 16 of these,
-// 12.8 us each = 6.8 % of the batch-16 step; every other finalize of the library was grouped already): blockIdx.y = job (its
-// srk_pw_wgrad_args from a device table; RI = Cin, R2 = CoutP, NR = nranges), blockIdx.x strides over the job's items.
-__global__ __launch_bounds__(256) void pw_wgrad_finalize_group_kernel(const srk_pw_wgrad_args* __restrict__ jobs) {
-  const srk_pw_wgrad_args a = jobs[blockIdx.y];
-  const long long fin = (long long)a.Chid * (a.Cin + a.CoutP) / 4 + a.Chid + a.CoutP;
-  for (long long gi = (long long)blockIdx.x * 256 + threadIdx.x; gi < fin; gi += (long long)gridDim.x * 256)
-    pw_fin_item(a, a.nranges, a.Cin, a.CoutP, gi);
-}
-
 // ------------------------------------------------------------------------------------------------------------------------------
 // packing: fp32 [Chid][Cin] / [Cmid][Chid] weights (+ biases) -> constant block + per-slice blocks of both directions
 //   fwd : cst = b1p[Chid] | b2p[R2] (padded to whole KB) ; slice s = W1 part | W2 part
@@ -1263,7 +1253,7 @@ template <int DT, int KC1, int NRB> int pw_bwd_launch(const srk_pw_bwd_args& a, 
   return 0;
 }
 
-template <int DT, int KC1, int NRB> int pw_wgrad_launch(const srk_pw_wgrad_args& a, hipStream_t st, int NR, bool finalize) {
+template <int DT, int KC1, int NRB> int pw_wgrad_launch(const srk_pw_wgrad_args& a, hipStream_t st, int NR) {
   typedef PwCfg<KC1, NRB> C;
   constexpr int PLANE = 64 * 128, BUF = (C::RI / 64 + C::R2 / 64) * PLANE, LDS = 3 * BUF + 2 * 4 * PLANE;
   static_assert(LDS <= 160 * 1024, "LDS");
@@ -1274,10 +1264,8 @@ template <int DT, int KC1, int NRB> int pw_wgrad_launch(const srk_pw_wgrad_args&
   const int NS = a.Chid / 128;                                   // slice pairs
   hipLaunchKernelGGL((pw_wgrad_kernel<DT, KC1, NRB>), dim3((unsigned)(NS * NR)), dim3(512), LDS, st, a,
                      (unsigned)(a.P * a.x_pitch * 2), (unsigned)(a.P * a.gz_pitch * 2), NR, (int)(ntiles / NR), (int)(ntiles % NR));
-  if (finalize) {
-    const long long fin = (long long)a.Chid * (C::RI + C::R2) / 4 + a.Chid + C::R2;
-    hipLaunchKernelGGL(pw_wgrad_finalize_kernel, dim3((unsigned)((fin + 255) / 256)), dim3(256), 0, st, a, NR, C::RI, C::R2);
-  }
+  const long long fin = (long long)a.Chid * (C::RI + C::R2) / 4 + a.Chid + C::R2;
+  hipLaunchKernelGGL(pw_wgrad_finalize_kernel, dim3((unsigned)((fin + 255) / 256)), dim3(256), 0, st, a, NR, C::RI, C::R2);
   SRK_LAUNCH_CHECK();
   return 0;
 }
@@ -1362,29 +1350,18 @@ extern "C" int srk_pw_backward(const srk_pw_bwd_args* a, srk_stream_t stream) {
 
 extern "C" int srk_pw_wgrad_ranges(long long P, int Chid) { return (P > 0 && Chid >= 64) ? pw_wgrad_ranges(P, Chid) : 0; }
 
-static int pw_wgrad_entry(const srk_pw_wgrad_args* a, srk_stream_t stream, bool finalize, const char* who) {
-  SRK_CHECK_ARG(a && a->x && a->gz && a->wpk && a->dw1p && a->dw2p && a->db1p && a->dw1 && a->dw2, "%s: null pointer", who);
-  SRK_CHECK_ARG(pw_shape_ok(a->Cin, a->Chid, a->CoutP) && a->dtype != SRK_F32 && a->Cmid <= a->CoutP, "%s: unsupported shape %d -> %d -> rows %d",
-                who, a->Cin, a->Chid, a->CoutP);
+extern "C" int srk_pw_wgrad(const srk_pw_wgrad_args* a, srk_stream_t stream) {
+  SRK_CHECK_ARG(a && a->x && a->gz && a->wpk && a->dw1p && a->dw2p && a->db1p && a->dw1 && a->dw2, "srk_pw_wgrad: null pointer");
+  SRK_CHECK_ARG(pw_shape_ok(a->Cin, a->Chid, a->CoutP) && a->dtype != SRK_F32 && a->Cmid <= a->CoutP, "srk_pw_wgrad: unsupported shape %d -> %d -> rows %d",
+                a->Cin, a->Chid, a->CoutP);
   SRK_CHECK_ARG(a->P > 0 && a->P * (long long)a->x_pitch * 2 < 0x7fff0000LL && a->P * (long long)a->gz_pitch * 2 < 0x7fff0000LL &&
                 a->x_pitch % 8 == 0 && a->x_coff % 8 == 0 && a->gz_pitch % 8 == 0 && a->gz_coff % 8 == 0 && a->Cz % 8 == 0 && a->Cz <= a->CoutP,
-                "%s: addressing (P=%lld)", who, a->P);
+                "srk_pw_wgrad: addressing (P=%lld)", a->P);
   const int NR = pw_wgrad_ranges(a->P, a->Chid);
-  SRK_CHECK_ARG(a->nranges == NR, "%s: nranges=%d but srk_pw_wgrad_ranges() is %d", who, a->nranges, NR);
+  SRK_CHECK_ARG(a->nranges == NR, "srk_pw_wgrad: nranges=%d but srk_pw_wgrad_ranges() is %d", a->nranges, NR);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (a->Cin == 128) return a->dtype == SRK_BF16 ? pw_wgrad_launch<SRK_BF16, 8, 4>(*a, st, NR, finalize) : pw_wgrad_launch<SRK_F16, 8, 4>(*a, st, NR, finalize);
-  return a->dtype == SRK_BF16 ? pw_wgrad_launch<SRK_BF16, 4, 2>(*a, st, NR, finalize) : pw_wgrad_launch<SRK_F16, 4, 2>(*a, st, NR, finalize);
-}
-
-extern "C" int srk_pw_wgrad(const srk_pw_wgrad_args* a, srk_stream_t stream) { return pw_wgrad_entry(a, stream, true, "srk_pw_wgrad"); }
-
-extern "C" int srk_pw_wgrad_partial(const srk_pw_wgrad_args* a, srk_stream_t stream) { return pw_wgrad_entry(a, stream, false, "srk_pw_wgrad_partial"); }
-
-extern "C" int srk_pw_wgrad_finalize_group(const srk_pw_wgrad_args* jobs_dev, int njobs, int blocks_per_job, srk_stream_t stream) {
-  SRK_CHECK_ARG(jobs_dev && njobs > 0 && njobs <= 65535 && blocks_per_job > 0, "srk_pw_wgrad_finalize_group: %d jobs, %d blocks each", njobs, blocks_per_job);
-  hipLaunchKernelGGL(pw_wgrad_finalize_group_kernel, dim3((unsigned)blocks_per_job, (unsigned)njobs), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), jobs_dev);
-  SRK_LAUNCH_CHECK();
-  return 0;
+  if (a->Cin == 128) return a->dtype == SRK_BF16 ? pw_wgrad_launch<SRK_BF16, 8, 4>(*a, st, NR) : pw_wgrad_launch<SRK_F16, 8, 4>(*a, st, NR);
+  return a->dtype == SRK_BF16 ? pw_wgrad_launch<SRK_BF16, 4, 2>(*a, st, NR) : pw_wgrad_launch<SRK_F16, 4, 2>(*a, st, NR);
 }
 
 #if SRK_PW_STAMPS

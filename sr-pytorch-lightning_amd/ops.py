@@ -11,7 +11,6 @@ cached per parameter version.
 Nothing here falls back to PyTorch arithmetic: every op raises if the tensors are
 not on a GPU or the HIP library is missing.
 """
-import contextlib
 import weakref
 
 import torch
@@ -168,355 +167,6 @@ def conv_pair_raw(x, pk1, pk2, *, out, relu_mid=False, scale_mid=1.0, mask=None,
     return out
 
 
-def _grad_target(p, shape, dev):
-    """Where the gradient of parameter `p` is to be WRITTEN, or None (a fresh tensor).  trainer.GradSync keeps all gradients in
-    one flat fp32 buffer (what the bucket all-reduces run on) and names each parameter's slice here: the weight-gradient
-    kernels then write the slice directly and autograd adopts a view of it as `.grad` -- no per-step pack copy.  Only while the
-    parameter has no gradient yet (an existing one is accumulated into, as before)."""
-    if p is None or not isinstance(p, torch.Tensor) or not p.is_leaf or p.grad is not None:
-        return None
-    t = p.__dict__.get("_srk_grad_target")
-    if t is None or tuple(t.shape) != tuple(shape) or t.device != dev:
-        return None
-    # only the FIRST use of the parameter in a backward pass gets the slice: `.grad` stays None until AccumulateGrad has seen every
-    # use, so a second use (a conv shared between two places of a user's model) would overwrite the first one's result in the same
-    # memory and autograd would then add two aliases of it (2 g_last instead of g_1 + g_2; ADVICE r3).  Later uses return fresh tensors.
-    pid = _pass_id()
-    if pid >= 0:
-        if p.__dict__.get("_srk_target_pass") == pid:
-            return None
-        p.__dict__["_srk_target_pass"] = pid
-    return t.detach()           # a fresh tensor object on the same memory (AccumulateGrad adopts a gradient nobody else references)
-
-
-def wgrad_raw(x, dy, *, N, H, W, Cin, Cout, k, w_shape, ps_r=0, scale=1.0, x_ps=0, dy_ps=0, want_bias=True, out_w=None, out_b=None):
-    """dW (OIHW fp32) and db for a conv whose input was `x` and output gradient is `dy`.
-    Cin/Cout are the padded storage channel counts of x / dy; w_shape the real OIHW shape.  out_w / out_b: write there."""
-    _need_gpu(x)
-    dev = x.device
-    cout, cin, kh, kw = w_shape
-    if N == 0:          # empty batch: zero gradients (the slab scratch would be uninitialised)
-        return (torch.zeros(w_shape, dtype=torch.float32, device=dev),
-                torch.zeros(cout, dtype=torch.float32, device=dev) if want_bias else None)
-    nck = _batch_chunks(N, x, dy)
-    if nck > 1:         # 2 GiB and more: sum the gradients of batch chunks (each chunk keeps the slab kernels)
-        step = -(-N // nck)
-        dw = db = None
-        for n0 in range(0, N, step):
-            n1 = min(N, n0 + step)
-            w_, b_ = wgrad_raw(x[n0:n1], dy[n0:n1], N=n1 - n0, H=H, W=W, Cin=Cin, Cout=Cout, k=k, w_shape=w_shape, ps_r=ps_r,
-                               scale=scale, x_ps=x_ps, dy_ps=dy_ps, want_bias=want_bias)
-            dw = w_ if dw is None else dw.add_(w_)
-            db = b_ if (db is None or b_ is None) else db.add_(b_)
-        if out_w is not None:
-            dw = out_w.copy_(dw)
-        if out_b is not None and db is not None:
-            db = out_b.copy_(db)
-        return dw, db
-    a = L.WgradArgs(x=x.data_ptr(), x_pitch=_pitch(x), x_coff=0, x_ps=int(x_ps),
-                    dy=dy.data_ptr(), dy_pitch=_pitch(dy), dy_coff=0, dy_ps=int(dy_ps),
-                    N=N, H=H, W=W, Cin=Cin, Cout=Cout, KH=k, KW=k, dwp=0, dbp=0, nslabs=0, dtype=_DT[x.dtype],
-                    cout_real=int(cout) if (ps_r <= 1 and not x_ps and not dy_ps) else 0)
-    nslabs = L.load().srk_wgrad_slabs(a)
-    couts = L.load().srk_wgrad_slab_cout(a)     # channels per slab row: Cout, or 4 (compact slabs: large kernel, <= 4 real output channels)
-    per = k * k * Cin * couts
-    if nslabs > 0:      # slab mode: every workgroup writes its own slab, nothing to zero
-        scratch = torch.empty(nslabs * (per + couts), dtype=torch.float32, device=dev)
-    else:               # atomic mode: one zeroed slab
-        scratch = torch.zeros(per + couts, dtype=torch.float32, device=dev)
-    ns = max(nslabs, 1)
-    dbp = scratch[ns * per:]
-    a.dwp, a.dbp, a.nslabs = scratch.data_ptr(), (dbp.data_ptr() if want_bias else 0), nslabs
-    L.call("srk_conv2d_wgrad", a, _stream())
-    dw = out_w if out_w is not None else torch.empty(w_shape, dtype=torch.float32, device=dev)
-    db = (out_b if out_b is not None else torch.empty(cout, dtype=torch.float32, device=dev)) if want_bias else None
-    # the unfolded head conv presents its OIHW weight as a 1x1 conv over Cin*KH*KW channels
-    f = L.WgradFinArgs(dwp=scratch.data_ptr(), dbp=dbp.data_ptr() if want_bias else 0, nslabs=nslabs, dw=dw.data_ptr(), db=_ptr(db),
-                       Cout=cout, Cin=(cin * kh * kw) // (k * k), KH=k, KW=k, CinP=Cin, CoutP=couts,
-                       ps_r=int(ps_r), scale=float(scale), accumulate=0)
-    L.call("srk_wgrad_finalize", f, _stream())
-    return dw, db
-
-
-# --------------------------------------------------------------------------------------------
-# deferred, grouped weight gradients
-# --------------------------------------------------------------------------------------------
-class _WgradQueue:
-    """Weight-gradient jobs of the backward pass in flight (one process per GPU: autograd's device thread appends,
-    the engine's final callback -- or a gradient-bucket hook -- flushes)."""
-
-    def __init__(self):
-        self.jobs = []          # dicts, see wgrad()
-        self.rjobs = []         # row-sum jobs (channel-attention parameter gradients), see defer_rowsum()
-        self.pwjobs = []        # finalize steps of pointwise-pair weight gradients (WDSR _Block_B), see pw_wgrad_raw()
-        self.armed = False      # somebody will flush (final callback queued, or inside hold_wgrads)
-        self.enabled = True
-        self.targets = {}       # address of a dw buffer -> number of jobs queued on it (weight sharing -> rounds)
-        self.gen = 0            # backward-pass generation (bumped by every flush)
-        self.stream = None      # stream of the backward pass (the flush launches there, whatever thread runs it)
-
-
-_WQ = _WgradQueue()
-_WG_BLOCKS_PER_JOB = 32
-import os as _os
-if _knob("SRK_NO_DEFER_WGRAD") == "1":      # A/B knob (tools/): every weight gradient as its own launch, like round 1
-    _WQ.enabled = False
-
-
-class hold_wgrads:
-    """Context manager for code that calls `wgrad` OUTSIDE an autograd backward pass (tests, micro-benchmarks): jobs are
-    queued inside the block and flushed as one grouped launch when it exits."""
-
-    def __enter__(self):
-        self.prev, _WQ.armed = _WQ.armed, True
-        return self
-
-    def __exit__(self, *exc):
-        _WQ.armed = self.prev
-        if not self.prev and exc[0] is None:
-            flush_wgrads()
-
-
-class hold_wgrads_discard:
-    """Like `hold_wgrads`, but the queued jobs are DROPPED on exit: a backward pass without its weight-gradient launches (bench.py times
-    a trunk's data-gradient launches this way; the parameters' .grad then hold unfilled buffers -- never use them)."""
-
-    def __enter__(self):
-        self.prev, _WQ.armed = _WQ.armed, True
-        return self
-
-    def __exit__(self, *exc):
-        discard_wgrads()
-        _WQ.armed = self.prev
-
-
-def set_defer_wgrad(enabled):
-    """Deferral switch (default on).  Off = every weight gradient is its own launch inside backward, which is what
-    code that reads gradients from inside backward needs (torch's DistributedDataParallel reducer)."""
-    prev = _WQ.enabled
-    _WQ.enabled = bool(enabled)
-    return prev
-
-
-def _grad_slot(p, shape):
-    """How a deferred job delivers the gradient of leaf `p`:  ('new', None)  -> a fresh tensor handed to autograd;
-    ('acc', tensor) -> accumulate into the existing fp32 gradient, autograd gets None;  None -> cannot defer."""
-    if p is None:
-        return ("new", None)
-    if isinstance(p, torch.Tensor) and p.__dict__.get("_srk_wn_proxy", False):
-        return ("new", None)            # effective weight of a weight-normed conv: its consumer (WeightNormGroup's backward) flushes first
-    if not (isinstance(p, torch.Tensor) and p.is_leaf and p.requires_grad):
-        return None
-    if getattr(p, "_backward_hooks", None):
-        return None                     # a tensor hook reads the gradient inside backward
-    hooks = getattr(p, "_post_accumulate_grad_hooks", None)
-    if hooks and not p.__dict__.get("_srk_flush_aware", False):
-        return None
-    g = p.grad
-    if g is None:
-        return ("new", None)
-    if g.dtype == torch.float32 and g.is_contiguous() and tuple(g.shape) == tuple(shape) and g.is_cuda:
-        return ("acc", g)
-    return None
-
-
-def _pass_id():
-    f = getattr(torch._C, "_current_graph_task_id", None)
-    return f() if f is not None else -1
-
-
-def _pass_slot(p, shape, device):
-    """Like `_grad_slot(p, shape)` for the [C]-sized parameters of BatchNorm / PReLU, which one module instance may see TWICE in one
-    forward (the reference's ResBlock appends the SAME norm / act instance behind both convs, common.py:94-100: SRResNet): returns
-    (tensor the finalize step adds into, or None;  tensor to hand to autograd, or None).  The first use of a pass hands a fresh
-    zero-free tensor to autograd and remembers it under the running backward pass's id; the second use ADDS into that tensor in
-    its own finalize step (autograd has not consumed it yet: AccumulateGrad runs after every use delivered) and hands over nothing --
-    else autograd adds the two [C]-sized gradients with a launch of its own, 33 of them per SRResNet step."""
-    sl = _grad_slot(p, shape)
-    if sl is not None and sl[0] == "acc":
-        return sl[1], None
-    pid = _pass_id()
-    if sl is None or pid < 0 or not isinstance(p, torch.Tensor):
-        return None, "new"
-    ent = p.__dict__.get("_srk_pass_grad")
-    if ent is not None and ent[0] == pid:
-        t = ent[1]()
-        if t is not None and tuple(t.shape) == tuple(shape) and t.device == device:
-            return t, None
-    return None, "new+remember"
-
-
-def _remember_pass_grad(p, t):
-    p.__dict__["_srk_pass_grad"] = (_pass_id(), weakref.ref(t))
-
-
-def _view_of(storage, shape, device, offset=0):
-    return torch.empty(0, dtype=torch.float32, device=device).set_(storage, int(offset), tuple(shape))
-
-
-def _arm_flush():
-    """Make sure somebody flushes the queues: the autograd engine's final callback of the running backward pass."""
-    if _WQ.armed:
-        return True
-    try:
-        torch.autograd.Variable._execution_engine.queue_callback(flush_wgrads)
-    except RuntimeError:            # not inside a backward pass (a Function's backward called by hand)
-        return False
-    _WQ.armed = True
-    return True
-
-
-class TableHolder:
-    """Owns the device tables (job descriptors of the grouped launches) of hipGraphs captured under `static_tables`: keep it alive as
-    long as the graphs, call `fence()` after the capture(s) and before the first replay."""
-
-    ARENA_BYTES = 1 << 20
-
-    def __init__(self):
-        self.tables = []
-        self.arena = None          # allocated by static_tables() OUTSIDE the capture: see take()
-        self.used = 0
-
-    def take(self, nbytes):
-        """`nbytes` of the arena (16-byte aligned), or None when it is full.  NOT memory of the graph's own pool: an allocation made
-        during the capture may reuse the address of an earlier temporary of the same graph, whose writer node would overwrite the
-        table in every replay (the in-graph upload sits behind that writer; a table written once does not)."""
-        n = (int(nbytes) + 15) // 16 * 16
-        if self.arena is None or self.used + n > self.arena.numel():
-            return None
-        t = self.arena[self.used:self.used + n]
-        self.used += n
-        self.tables.append(t)
-        return t
-
-    def fence(self):
-        if self.tables:
-            L.check(L.load().srk_upload_fence(), "srk_upload_fence")
-
-
-class _StaticTables:
-    holder = None
-
-
-@contextlib.contextmanager
-def static_tables(holder):
-    """Capture sites that own their graphs wrap the capture in this: the descriptor tables of the grouped launches (weight gradients,
-    finalizes, row sums, weight normalisation) are then written ONCE, at capture time, instead of by upload launches inside the graph
-    (3 per EDSR step, 30 per RCAN step at batch 16: include/srk.h, srk_upload_eager).  Valid because every address a replay sees is the
-    capture's; the holder keeps the tables' memory from being reused inside the graph's pool.  Foreign captures (a user's own
-    torch.cuda.graph around a step) keep the in-graph uploads."""
-    ok = _STATIC_TABLES
-    if ok:
-        try:
-            L.check(L.load().srk_upload_prepare(), "srk_upload_prepare")
-        except RuntimeError:          # an older library loaded through SRK_LIB_PATH (A/B runs)
-            ok = False
-    if ok and holder.arena is None and not torch.cuda.is_current_stream_capturing():
-        holder.arena = torch.empty(holder.ARENA_BYTES, dtype=torch.uint8, device=torch.device("cuda", torch.cuda.current_device()))
-        # the arena comes from the caching allocator on the ambient stream and is written from the library's upload stream: whatever that
-        # memory was last used for must have finished first (explicit, not a side effect of torch.cuda.graph's own synchronize)
-        torch.cuda.current_stream().synchronize()
-    prev, _StaticTables.holder = _StaticTables.holder, (holder if ok else None)
-    try:
-        yield holder
-    finally:
-        _StaticTables.holder = prev
-
-
-@contextlib.contextmanager
-def graph_capture(g, **kw):
-    """`torch.cuda.graph(g, **kw)` for a graph whose owner is this package: the grouped launches' tables are static (static_tables),
-    kept alive by the graph object itself."""
-    holder = TableHolder()
-    try:
-        with static_tables(holder):
-            with torch.cuda.graph(g, **kw):
-                yield holder
-    finally:
-        holder.fence()
-    g._srk_tables = holder
-
-
-def _upload_table(host_addr, nbytes, alloc, dev, st):
-    """Host bytes -> a fresh device table of `alloc` bytes on stream `st` (see static_tables)."""
-    h = _StaticTables.holder
-    if h is not None and h.arena is not None and h.arena.device == torch.device(dev) and torch.cuda.is_current_stream_capturing():
-        table = h.take(alloc)
-        if table is not None:
-            L.check(L.load().srk_upload_eager(table.data_ptr(), host_addr, nbytes), "srk_upload_eager")
-            return table
-    table = torch.empty(alloc, dtype=torch.uint8, device=dev)
-    L.check(L.load().srk_upload_small(table.data_ptr(), host_addr, nbytes, st), "srk_upload_small")
-    return table
-
-
-def _launch_rowsums(rjobs, st):
-    import ctypes as C
-    n = len(rjobs)
-    host = (L.RowsumJob * n)()
-    for i, j in enumerate(rjobs):
-        host[i].src, host[i].dst, host[i].n, host[i].k = j["src"].data_ptr(), j["dst"], j["n"], j["k"]
-    nbytes = C.sizeof(L.RowsumJob) * n
-    table = _upload_table(C.addressof(host), nbytes, _roundup(nbytes, 16), rjobs[0]["src"].device, st)
-    L.check(L.load().srk_rowsum_group(table.data_ptr(), n, max(j["k"] for j in rjobs), st), "srk_rowsum_group")
-
-
-def _launch_pw_finalize(pwjobs, st):
-    """ONE launch sums the slabs of every queued pointwise-pair weight gradient (srk_pw_wgrad_finalize_group)."""
-    import ctypes as C
-    n = len(pwjobs)
-    host = (L.PwWgradArgs * n)(*[j["a"] for j in pwjobs])
-    nbytes = C.sizeof(L.PwWgradArgs) * n
-    table = _upload_table(C.addressof(host), nbytes, _roundup(nbytes, 16), pwjobs[0]["keep"][0].device, st)
-    items = max((j["a"].Chid * (j["a"].Cin + j["a"].CoutP)) // 4 + j["a"].Chid + j["a"].CoutP for j in pwjobs)
-    bpj = max(1, min((items + 255) // 256, 256))           # one item per thread: the launch is a 30 MB-per-job read, latency-bound with fewer blocks
-    L.check(L.load().srk_pw_wgrad_finalize_group(table.data_ptr(), n, bpj, st), "srk_pw_wgrad_finalize_group")
-    for j in pwjobs:
-        j["keep"].append(table)
-
-
-def defer_rowsum(per, params, shapes_offsets):
-    """Sum `per` [n][K] over n into a fresh [K] buffer whose slices become the gradients of `params` -- deferred to the end of
-    the backward pass, where ONE launch serves every queued job (an RCAN backward has 200 of them).
-
-    shapes_offsets[i] = (shape, offset into the K floats) of parameter i's gradient.  Returns the list of gradient tensors
-    (views of the unfilled buffer, which autograd adopts as `.grad`), or None when deferral does not apply (a gradient
-    already exists and autograd would read the unfilled buffer, hooks, a second use of the parameters in this pass...)."""
-    if not _WQ.enabled or per.shape[0] == 0:
-        return None
-    for p, (shape, _) in zip(params, shapes_offsets):
-        sl = _grad_slot(p, shape)
-        if sl is None or sl[0] != "new" or p is None:
-            return None
-        seen = p.__dict__.get("_srk_pending_rs")
-        if seen is not None and seen == _WQ.gen:
-            # used twice in this pass: autograd will ADD this gradient to the (still unfilled) one queued earlier, right
-            # after this backward returns -- fill the queued ones now (stream order puts the sums in front of that add)
-            rj, _WQ.rjobs = _WQ.rjobs, []
-            if rj:
-                with torch.cuda.stream(_WQ.stream):
-                    _launch_rowsums(rj, _WQ.stream.cuda_stream)
-            return None
-    if not _arm_flush():
-        return None
-    n, k = per.shape
-    tot = torch.empty(k, dtype=torch.float32, device=per.device)
-    stg = tot.untyped_storage()
-    outs, new = [], []
-    for p, (shape, off) in zip(params, shapes_offsets):
-        numel = 1
-        for d in shape:
-            numel *= d
-        v = tot[off:off + numel].view(shape)
-        new.append((p, v.data_ptr(), stg, tuple(shape), off))
-        p.__dict__["_srk_pending_rs"] = _WQ.gen
-        outs.append(v)
-    _WQ.rjobs.append(dict(src=per, dst=tot.data_ptr(), n=int(n), k=int(k), keep=[per, stg], new=new))
-    _WQ.stream = torch.cuda.current_stream()
-    del tot
-    return outs
-
-
 _ONES = {}
 
 
@@ -533,137 +183,6 @@ def backward(loss):
             return
         one = _ONES[key] = torch.ones((), dtype=loss.dtype, device=loss.device)
     loss.backward(gradient=one if loss.dim() == 0 else one.expand_as(loss))
-
-
-def discard_wgrads():
-    """Drop whatever a backward pass that did NOT end normally left queued (an exception inside backward, a failed hipGraph
-    capture: the engine's final callback may never have run, so `armed` would stay set and later passes would queue jobs
-    nobody flushes).  Call before starting a fresh step."""
-    _WQ.jobs, _WQ.rjobs, _WQ.pwjobs, _WQ.armed, _WQ.targets = [], [], [], False, {}
-    _WQ.gen += 1
-
-
-def flush_wgrads():
-    """Launch every queued weight gradient: ONE grouped slab kernel per dtype and ONE grouped finalize per round."""
-    import ctypes as C
-    jobs, _WQ.jobs, _WQ.armed, _WQ.targets = _WQ.jobs, [], False, {}
-    rjobs, _WQ.rjobs = _WQ.rjobs, []
-    pwjobs, _WQ.pwjobs = _WQ.pwjobs, []
-    _WQ.gen += 1
-    if not jobs and not rjobs and not pwjobs:
-        return
-    lib = L.load()
-    stream = _WQ.stream if _WQ.stream is not None else torch.cuda.current_stream()
-    with torch.cuda.stream(stream):         # the flush may run on another thread than the backward nodes: same stream
-        st = stream.cuda_stream
-        if rjobs:
-            _launch_rowsums(rjobs, st)
-        if pwjobs:
-            _launch_pw_finalize(pwjobs, st)
-        for dt in sorted({j["a"].dtype for j in jobs}):
-            grp = [j for j in jobs if j["a"].dtype == dt]
-            n = len(grp)
-            arr = (L.WgradArgs * n)(*[j["a"] for j in grp])
-            nblocks, sfl = C.c_int(0), C.c_longlong(0)
-            L.check(lib.srk_wgrad_group_plan(arr, n, None, None, None, C.byref(nblocks), C.byref(sfl)), "srk_wgrad_group_plan")
-            dev = grp[0]["keep"][0].device
-            scratch = torch.empty(sfl.value, dtype=torch.float32, device=dev)
-            jb = lib.srk_wgrad_group_job_bytes()
-            off_bj = _roundup(n * jb, 16)
-            off_fin = _roundup(off_bj + 4 * nblocks.value, 16)
-            fin_sz = C.sizeof(L.WgradFinArgs)
-            total = _roundup(off_fin + n * fin_sz, 16)
-            host = (C.c_ubyte * total)()
-            base = C.addressof(host)
-            L.check(lib.srk_wgrad_group_plan(arr, n, scratch.data_ptr(), base, base + off_bj, C.byref(nblocks), C.byref(sfl)),
-                    "srk_wgrad_group_plan")
-            # finalize table ordered by round (a job that accumulates into a buffer another job of this pass writes comes later)
-            order = sorted(range(n), key=lambda i: grp[i]["round"])
-            rounds = {}
-            for pos, i in enumerate(order):
-                a, f = arr[i], grp[i]
-                fa = L.WgradFinArgs(dwp=a.dwp, dbp=a.dbp or 0, nslabs=a.nslabs, dw=f["dw"], db=f["db"], Cout=f["Cout"], Cin=f["Cin"],
-                                    KH=3, KW=3, CinP=a.Cin, CoutP=a.Cout, ps_r=f["ps_r"], scale=f["scale"], accumulate=f["acc"])
-                C.memmove(base + off_fin + pos * fin_sz, C.addressof(fa), fin_sz)
-                rounds.setdefault(f["round"], [pos, 0])[1] += 1
-            table = _upload_table(base, total, total, dev, st)
-            L.check(lib.srk_conv2d_wgrad_group(table.data_ptr(), table.data_ptr() + off_bj, nblocks.value, dt, st), "srk_conv2d_wgrad_group")
-            # workgroups per job: one per (2 input channels x 64 output channels) tile of the largest job, 32..256
-            tiles = max(((a_.Cin + 1) // 2) * ((a_.Cout + 63) // 64) for a_ in arr)
-            bpj = max(_WG_BLOCKS_PER_JOB, min(256, tiles))
-            for r in sorted(rounds):
-                pos, cnt = rounds[r]
-                L.check(lib.srk_wgrad_finalize_group(table.data_ptr() + off_fin + pos * fin_sz, cnt, bpj, st), "srk_wgrad_finalize_group")
-        # a gradient autograd COPIED instead of adopting (create_graph, layout contract) holds the bytes of the then
-        # unfilled buffer: refresh it from the filled one.  ('new' jobs only: .grad was None, so the copy is all it holds)
-        with torch.no_grad():
-            for j in jobs + rjobs:
-                for ent in j["new"]:
-                    p, ptr, stg, shape = ent[:4]
-                    if p is not None and p.__dict__.get("_srk_wn_proxy", False):
-                        continue                    # non-leaf: the gradient went to WeightNormGroup's backward by address
-                    g = p.grad if p is not None else None
-                    if g is not None and g.data_ptr() != ptr and tuple(g.shape) == tuple(shape):
-                        g.copy_(_view_of(stg, shape, g.device, ent[4] if len(ent) > 4 else 0))
-    # `table`, `scratch`, operands and result storages are referenced by enqueued work only from here on: the caching
-    # allocator re-issues a freed block on this stream behind these launches
-
-
-def wgrad(x, dy, *, wparam=None, bparam=None, **kw):
-    """Weight (+ bias) gradient of one conv.  3x3 16-bit convs whose parameters are leaves are QUEUED and computed by
-    one grouped launch when the backward pass ends (`flush_wgrads`, the autograd engine's final callback); everything
-    else runs now (`wgrad_raw`).  Returns what backward() hands to autograd for (weight, bias).
-
-    A queued job returns EMPTY tensors that autograd adopts as `.grad` (AccumulateGrad takes over a gradient nobody else
-    references); the queue keeps their storages -- not the tensors -- alive and the flush fills them by address."""
-    want_bias = kw.get("want_bias", True)
-    k, w_shape = kw["k"], kw["w_shape"]
-    tw = _grad_target(wparam, w_shape, x.device)
-    tb = _grad_target(bparam, (w_shape[0],), x.device) if want_bias else None
-    if not (_WQ.enabled and k == 3 and x.dtype in (torch.bfloat16, torch.float16) and kw["N"] > 0 and kw.get("x_ps", 0) <= 1):
-        return wgrad_raw(x, dy, out_w=tw, out_b=tb, **kw)
-    sw = _grad_slot(wparam, w_shape)
-    sb = _grad_slot(bparam, (w_shape[0],)) if want_bias else ("new", None)
-    if sw is None or sb is None or wparam is None or (want_bias and sb[0] != sw[0]) or _batch_chunks(kw["N"], x, dy) > 1:
-        return wgrad_raw(x, dy, out_w=tw, out_b=tb, **kw)
-    a = L.WgradArgs(x=x.data_ptr(), x_pitch=_pitch(x), x_coff=0, x_ps=int(kw.get("x_ps", 0)),
-                    dy=dy.data_ptr(), dy_pitch=_pitch(dy), dy_coff=0, dy_ps=int(kw.get("dy_ps", 0)),
-                    N=kw["N"], H=kw["H"], W=kw["W"], Cin=kw["Cin"], Cout=kw["Cout"], KH=3, KW=3, dwp=0, dbp=1 if want_bias else 0,
-                    nslabs=0, dtype=_DT[x.dtype])
-    if not L.load().srk_wgrad_group_ok(a):
-        return wgrad_raw(x, dy, out_w=tw, out_b=tb, **kw)
-    cout, cin = w_shape[0], w_shape[1]
-    dev = x.device
-    ret_w = ret_b = None
-    keep = [x, dy]
-    new = []
-    if sw[0] == "new":
-        seen = wparam.__dict__.get("_srk_pending")          # second use of a shared weight in this pass -> accumulate round
-        if seen is not None and seen[0] == _WQ.gen:
-            dw_ptr, db_ptr, acc = seen[1], seen[2], 1
-        else:
-            ret_w = tw if tw is not None else torch.empty(w_shape, dtype=torch.float32, device=dev)
-            ret_b = (tb if tb is not None else torch.empty(cout, dtype=torch.float32, device=dev)) if want_bias else None
-            dw_ptr, db_ptr, acc = ret_w.data_ptr(), _ptr(ret_b), 0
-            sw_stg = ret_w.untyped_storage()
-            keep.append(sw_stg)
-            new.append((wparam, dw_ptr, sw_stg, w_shape, ret_w.storage_offset()))
-            if ret_b is not None:
-                sb_stg = ret_b.untyped_storage()
-                keep.append(sb_stg)
-                new.append((bparam, db_ptr, sb_stg, (cout,), ret_b.storage_offset()))
-            wparam.__dict__["_srk_pending"] = (_WQ.gen, dw_ptr, db_ptr)
-    else:
-        dw_ptr, db_ptr, acc = sw[1].data_ptr(), (sb[1].data_ptr() if want_bias else 0), 1
-        keep += [sw[1], sb[1]]
-    rnd = _WQ.targets.get(dw_ptr, 0)                        # jobs on one buffer finalize in successive rounds
-    _WQ.targets[dw_ptr] = rnd + 1
-    _WQ.jobs.append(dict(a=a, dw=dw_ptr, db=db_ptr, Cout=cout, Cin=cin, ps_r=int(kw.get("ps_r", 0)), scale=float(kw.get("scale", 1.0)),
-                         acc=acc, round=rnd, keep=keep, new=new))
-    _WQ.stream = torch.cuda.current_stream()
-    if not _arm_flush():                # not inside a backward pass (a Function's backward called by hand)
-        flush_wgrads()
-    return ret_w, ret_b
 
 
 def unfold_raw(x, sub, k, dtype):
@@ -748,7 +267,6 @@ def nhwc_to_nchw(x, C):
 # autograd Functions
 # --------------------------------------------------------------------------------------------
 _RES_LINK = _knob("SRK_NO_RES_LINK", "0") != "1"        # A/B knob
-_STATIC_TABLES = _knob("SRK_NO_STATIC_TABLES", "0") != "1"      # A/B knob: descriptor tables written once per captured graph (static_tables)
 
 
 class ResLink:
@@ -817,9 +335,10 @@ class ConvFn(torch.autograd.Function):
                 if ctx.link is not None and ctx.link.g is not None:        # the block's residual gradient: added by this launch
                     parked, ctx.link.g = ctx.link.g, None
                 conv_raw(g, pkd, N=n, H=h, W=wd, Cin=coutp, Cout=cinp, out=gx, scale=scale, x_ps=ps_r, use_bias=False, res=parked)
-        if ctx.needs_input_grad[1]:
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
             gw, gb = wgrad(x, g, wparam=ctx.wb[0], bparam=ctx.wb[1], N=n, H=h, W=wd, Cin=cinp, Cout=coutp, k=k,
                            w_shape=tuple(w.shape), ps_r=ps_r, scale=scale, dy_ps=ps_r, want_bias=has_b)
+            gw = gw if ctx.needs_input_grad[1] else None
         return gx, gw, gb, (g if has_res else None), None, None, None
 
 
@@ -853,9 +372,10 @@ class HeadConvFn(torch.autograd.Function):
         g = g.contiguous()
         n, h, wd, kp = xu.shape
         gw = gb = None
-        if ctx.needs_input_grad[1]:
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
             gw, gb = wgrad_raw(xu, g, N=n, H=h, W=wd, Cin=kp, Cout=g.shape[3], k=1, w_shape=tuple(w.shape),
                                want_bias=ctx.has_b)
+            gw = gw if ctx.needs_input_grad[1] else None
         return None, gw, gb, None, None
 
 
@@ -903,9 +423,10 @@ class TailConvFn(torch.autograd.Function):
             pkd = pack_conv(w, None, x.dtype, dgrad=True, token=ctx.pg)
             gx = torch.empty_like(x)
             conv_raw(dy, pkd, N=n, H=h, W=wd, Cin=dy.shape[3], Cout=cinp, out=gx, use_bias=False)
-        if ctx.needs_input_grad[1]:
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
             gw, gb = wgrad(x, dy, wparam=ctx.wb[0], bparam=ctx.wb[1], N=n, H=h, W=wd, Cin=cinp, Cout=dy.shape[3], k=k,
                            w_shape=tuple(w.shape), want_bias=has_b)
+            gw = gw if ctx.needs_input_grad[1] else None
         return gx, gw, gb, (g if has_res else None), None, None
 
 
@@ -937,10 +458,11 @@ class SkipConvFn(torch.autograd.Function):
         ps_r, has_b = ctx.cfg
         n, h, wd, kp = xu.shape
         gw = gb = None
-        if ctx.needs_input_grad[1]:
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
             dy = to_nhwc(g, xu.dtype, ps_r=ps_r)
             gw, gb = wgrad_raw(xu, dy, N=n, H=h, W=wd, Cin=kp, Cout=dy.shape[3], k=1, w_shape=tuple(w.shape),
                                want_bias=has_b)
+            gw = gw if ctx.needs_input_grad[1] else None
         return None, gw, gb, None, None, None
 
 
@@ -1041,14 +563,10 @@ class HrTailFn(torch.autograd.Function):
             scratch = torch.empty(int(L.load().srk_hrtail_scratch_floats(n, ci)), dtype=f32, device=dev)
             ptrs = {k: v.data_ptr() for k, v in red.items()}
             L.call("srk_hrtail_edge_bwd_w", HrTailFn._args(x, wu_, bu_, wt_, None, bufs, g=g.data_ptr(), scratch=scratch.data_ptr(), **ptrs), st)
-            # (written straight into trainer.GradSync's flat buffer when the parameters name a slice of it: _grad_target)
-            def dest(p, shape):
-                t = _grad_target(p, shape, dev) if p is not None and p.dtype == f32 else None
-                return t if t is not None else torch.empty(shape, dtype=f32, device=dev)
             pu, pbu, pt, pbt = ctx.wb
-            gwu, gwt = dest(pu, tuple(wu_.shape)), dest(pt, tuple(wt_.shape))
-            gbu = dest(pbu, (4 * c,)) if has_bu else None
-            gbt = dest(pbt, (o,)) if has_bt else None
+            gwu, gwt = (route(p, shape, dev, slice=p.dtype == f32, buffer=True).out for p, shape in ((pu, tuple(wu_.shape)), (pt, tuple(wt_.shape))))
+            gbu = route(pbu, (4 * c,), dev, slice=pbu.dtype == f32, buffer=True).out if has_bu else None
+            gbt = route(pbt, (o,), dev, slice=pbt.dtype == f32, buffer=True).out if has_bt else None
             L.call("srk_hrtail_expand", HrTailFn._args(x, wu_, bu_, wt_, None, bufs, r=r.data_ptr(), r0=r0.data_ptr(), dwt=gwt.data_ptr(),
                                                        dbt=_ptr(gbt), dwu=gwu.data_ptr(), dbu=_ptr(gbu), **ptrs), st)
         return gx, gwu, gbu, gwt, gbt, None
@@ -1118,20 +636,21 @@ class ConvChainFn(torch.autograd.Function):
                                pack_conv(ws[0], None, g.dtype, dgrad=True, token=ctx.pg), out=torch.empty_like(g),
                                scale_mid=scale, mask=y1, mid=g1, res=g, use_bias=False)
             for i, (a_in, d, sc) in enumerate(((x, g1, 1.0), (y1, g, scale))):
-                if ctx.needs_input_grad[3 + 2 * i]:
-                    grads[2 * i], grads[2 * i + 1] = wgrad(
+                if ctx.needs_input_grad[3 + 2 * i] or ctx.needs_input_grad[4 + 2 * i]:
+                    gw, grads[2 * i + 1] = wgrad(
                         a_in, d, wparam=ctx.wb[0][i], bparam=ctx.wb[1][i], N=n, H=h, W=wd, Cin=64, Cout=64, k=3,
                         w_shape=tuple(ws[i].shape), scale=sc, want_bias=has_b[i])
+                    grads[2 * i] = gw if ctx.needs_input_grad[3 + 2 * i] else None
             return (gx, None, None, *grads)
         for i in range(L_ - 1, -1, -1):
             w = ws[i]
             a_in = acts[i]
             k = w.shape[2]
             sc = scale if i == L_ - 1 else 1.0
-            if ctx.needs_input_grad[3 + 2 * i]:
+            if ctx.needs_input_grad[3 + 2 * i] or ctx.needs_input_grad[4 + 2 * i]:
                 gw, gb = wgrad(a_in, dy, wparam=ctx.wb[0][i], bparam=ctx.wb[1][i], N=n, H=h, W=wd, Cin=a_in.shape[3],
                                Cout=dy.shape[3], k=k, w_shape=tuple(w.shape), scale=sc, want_bias=has_b[i])
-                grads[2 * i], grads[2 * i + 1] = gw, gb
+                grads[2 * i], grads[2 * i + 1] = (gw if ctx.needs_input_grad[3 + 2 * i] else None), gb
             pkd = pack_conv(w, None, g.dtype, dgrad=True, token=ctx.pg)
             gin = torch.empty_like(a_in)
             mk = a_in if (i > 0 and relus[i - 1]) else None
@@ -1273,9 +792,10 @@ class ResTrunkFn(torch.autograd.Function):
         for b in range(nb - 1, -1, -1):
             jobs += [(2 * b + 1, hs[b], gxs[b + 1], scale), (2 * b, xs[b], ghs[b], 1.0)]
         for i, a_in, dy, sc in jobs:
-            if ctx.needs_input_grad[3 + 2 * i]:
-                grads[2 * i], grads[2 * i + 1] = wgrad(a_in, dy, wparam=ctx.wb[0][i], bparam=ctx.wb[1][i], N=n, H=h, W=wd, Cin=64, Cout=64, k=3,
-                                                       w_shape=(64, 64, 3, 3), scale=sc, want_bias=has_b[i])
+            if ctx.needs_input_grad[3 + 2 * i] or ctx.needs_input_grad[4 + 2 * i]:
+                gw, grads[2 * i + 1] = wgrad(a_in, dy, wparam=ctx.wb[0][i], bparam=ctx.wb[1][i], N=n, H=h, W=wd, Cin=64, Cout=64, k=3,
+                                             w_shape=(64, 64, 3, 3), scale=sc, want_bias=has_b[i])
+                grads[2 * i] = gw if ctx.needs_input_grad[3 + 2 * i] else None
         return (gx, None, None, *grads)
 
 
@@ -1439,7 +959,7 @@ class WeightNormGroup:
         _need_gpu(params[0])
         ws = _WnFn.apply(self, *params)
         for w, c in zip(ws, self.convs):
-            w.__dict__["_srk_wn_proxy"] = True
+            mark_proxy(w)
             w.__dict__["_srk_pack_key"] = ("wn", id(c.weight_v))
         return list(ws)
 
@@ -1462,7 +982,6 @@ def pw_ok(x, w1, w2):
     return bool(L.load().srk_pw_shape_ok(int(w1.shape[1]), int(w1.shape[0]), _roundup(int(w2.shape[0]), 64)))
 
 
-
 def pw_forward_raw(x, pk, out):
     n, h, wd, _ = x.shape
     L.call("srk_pw_forward", L.PwArgs(x=x.data_ptr(), x_pitch=_pitch(x), x_coff=0, P=n * h * wd, Cin=pk.cin, Chid=pk.chid, CoutP=pk.coutp,
@@ -1480,7 +999,7 @@ def pw_backward_raw(x, gz, pk, gx, *, res=None, h_out=None, gh_out=None):
     return gx
 
 
-def pw_wgrad_raw(x, gz, pk, w1_shape, w2_shape, want_b1=True, want_b2=True, defer=False):
+def pw_wgrad_raw(x, gz, pk, w1_shape, w2_shape, want_b1=True, want_b2=True):
     """dW1, db1, dW2, db2 of the pointwise pair from x and gz alone (srk_pw_wgrad: h and gh are re-computed tile by tile)."""
     n, h, wd, _ = x.shape
     P = n * h * wd
@@ -1500,32 +1019,16 @@ def pw_wgrad_raw(x, gz, pk, w1_shape, w2_shape, want_b1=True, want_b2=True, defe
         dw1p=scratch.data_ptr(), dw2p=scratch.data_ptr() + 4 * o2, db1p=scratch.data_ptr() + 4 * o3,
         db2p=(scratch.data_ptr() + 4 * o4) if want_b2 else 0, nranges=nr,
         dw1=dw1.data_ptr(), db1=_ptr(db1), dw2=dw2.data_ptr(), db2=_ptr(db2), dtype=_DT[x.dtype])
-    if defer and _WQ.enabled and not _PW_FIN_EACH and _arm_flush():
-        # inside a backward pass: the slabs now, their sums with every other pointwise pair's in ONE launch when the pass's deferred
-        # weight gradients are flushed (the results are read no earlier: WeightNormGroup's node flushes first)
-        L.call("srk_pw_wgrad_partial", a, _stream())
-        # (the STORAGES, not the tensors: AccumulateGrad adopts a gradient nobody else references, and clones -- now, unfilled -- one that is)
-        _WQ.pwjobs.append(dict(a=a, keep=[scratch] + [t.untyped_storage() for t in (dw1, db1, dw2, db2) if t is not None]))
-        _WQ.stream = torch.cuda.current_stream()
-    else:
-        L.call("srk_pw_wgrad", a, _stream())
+    L.call("srk_pw_wgrad", a, _stream())
     return dw1, db1, dw2, db2
-
-
-# One finalize launch for ALL pointwise pairs of a backward pass (srk_pw_wgrad_finalize_group) is OFF by default: measured on two boxes
-# (tools/ab_pw.sh, profiles/r5_ab_pw_b16.txt) it is -1 % ... +0.5 % against a finalize per pair -- each pair's 31.5 MB of slabs are still in the
-# Infinity Cache when its own finalize reads them right behind the kernel that wrote them; all sixteen read at the end of the pass (504 MB) come
-# from HBM.  SRK_DEBUG=1 SRK_PW_GROUP_FIN=1 selects the grouped form.
-_PW_FIN_EACH = _knob("SRK_PW_GROUP_FIN", "0") != "1"
-_PW_WG_OFF = _knob("SRK_NO_PW_WGRAD", "0") == "1"      # A/B knob: h / gh through HBM + the two 1x1 weight-gradient GEMMs
 
 
 class WdsrBlockBFn(torch.autograd.Function):
     """WDSR _Block_B (models/wdsr.py:30-51): out = conv3x3(conv1x1(relu(conv1x1(x)))) * res_scale + x.
 
     forward : srk_pw_forward (both pointwise convs, the 6F-channel tensor never leaves the chip) + one srk_conv2d (3x3, * scale, + x)
-    backward: dgrad 3x3 (* scale), srk_pw_backward (re-computes the ReLU mask, + g of the skip connection; also leaves h and gh
-              for the pointwise weight gradients), three weight gradients."""
+    backward: dgrad 3x3 (* scale), srk_pw_backward (re-computes the ReLU mask, + g of the skip connection), the 3x3 weight gradient
+              and srk_pw_wgrad (both pointwise weight gradients, h and gh re-computed tile by tile)."""
 
     @staticmethod
     def forward(ctx, x, scale, w1, b1, w2, b2, w3, b3):
@@ -1560,20 +1063,8 @@ class WdsrBlockBFn(torch.autograd.Function):
         gw3, gb3 = wgrad(z, g, wparam=ctx.wb[4], bparam=b3, N=n, H=h, W=wd, Cin=z.shape[3], Cout=cp, k=3, w_shape=tuple(w3.shape),
                          scale=scale, want_bias=b3 is not None)
         gx = torch.empty_like(x)
-        if _PW_WG_OFF:
-            hid = torch.empty((n, h, wd, pk.chid), dtype=dt, device=x.device)
-            ghid = torch.empty_like(hid)
-            pw_backward_raw(x, gz, pk, gx, res=g, h_out=hid, gh_out=ghid)
-            gw2, gb2 = wgrad(hid, gz, wparam=ctx.wb[2], bparam=b2, N=n, H=h, W=wd, Cin=pk.chid, Cout=gz.shape[3], k=1, w_shape=tuple(w2.shape),
-                             want_bias=b2 is not None)
-            gw1, gb1 = wgrad(x, ghid, wparam=ctx.wb[0], bparam=b1, N=n, H=h, W=wd, Cin=cp, Cout=pk.chid, k=1, w_shape=tuple(w1.shape),
-                             want_bias=b1 is not None)
-            return gx, None, gw1, gb1, gw2, gb2, gw3, gb3
         pw_backward_raw(x, gz, pk, gx, res=g)
-        # deferred finalize only where autograd will ADOPT the (still unfilled) results: no existing .grad to accumulate into, no hooks
-        can_defer = all((sl := _grad_slot(p_, sh_)) is not None and sl[0] == "new"
-                        for p_, sh_ in ((ctx.wb[0], tuple(w1.shape)), (b1, (w1.shape[0],)), (ctx.wb[2], tuple(w2.shape)), (b2, (w2.shape[0],))))
-        gw1, gb1, gw2, gb2 = pw_wgrad_raw(x, gz, pk, tuple(w1.shape), tuple(w2.shape), want_b1=b1 is not None, want_b2=b2 is not None, defer=can_defer)
+        gw1, gb1, gw2, gb2 = pw_wgrad_raw(x, gz, pk, tuple(w1.shape), tuple(w2.shape), want_b1=b1 is not None, want_b2=b2 is not None)
         return gx, None, gw1, gb1, gw2, gb2, gw3, gb3
 
 
@@ -2007,8 +1498,10 @@ def rdb(x, convs, lff, dest=None):
 
 
 # --------------------------------------------------------------------------------------------
-# op families that live in their own modules (round 6): everything they define is part of this namespace, as before
+# gradient routing and the op families that live in their own modules: everything they define is part of this namespace, as before
 # --------------------------------------------------------------------------------------------
+from .grads import *         # noqa: E402,F401,F403  parameter-gradient routing and the deferred queue: wgrad, flush_wgrads, graph_capture, ...
+from .grads import _WQ, _upload_table      # noqa: E402,F401
 from .ops_norm import *      # noqa: E402,F401,F403  BatchNorm2d, PReLU, per-channel statistics
 from .ops_proj import *      # noqa: E402,F401,F403  unfold / fold, projection and general strided convs
 from .ops_proj import _proj_launch      # noqa: E402,F401  (bench.py / tools/microbench_proj.py time the raw launches)

@@ -5,7 +5,8 @@ import os
 import torch
 
 from . import _lib as L
-from .ops import _DT, _f32c, _grad_slot, _knob, _need_gpu, _pass_slot, _pitch, _ptr, _remember_pass_grad, _stream      # (ops.py imports this module at its END: these exist by then)
+from .grads import route
+from .ops import _DT, _f32c, _knob, _need_gpu, _pitch, _ptr, _stream      # (ops.py imports this module at its END: these exist by then)
 
 
 def chan_sums(x, y=None, mode=None, shift=None):
@@ -180,11 +181,9 @@ class PReLUFn(torch.autograd.Function):
             gx = torch.empty_like(g)
             gate = (gx, sl)
         one = weight.numel() == 1
-        slot = _grad_slot(ctx.wparam, tuple(weight.shape))      # an existing fp32 .grad: the finalize step adds into it
-        acc = slot[1] if (slot is not None and slot[0] == "acc") else None
-        s = chan_reduce(x, g, 2, None, 4, 1, total=one, creal=None if one else weight.numel(), dgamma_acc=acc, gate=gate)[0]
-        gw = None if acc is not None else (s[:1] if one else s[:weight.numel()])
-        return gx, gw
+        r = route(ctx.wparam, tuple(weight.shape), accumulate=True)      # an existing fp32 .grad: the finalize step adds into it
+        s = chan_reduce(x, g, 2, None, 4, 1, total=one, creal=None if one else weight.numel(), dgamma_acc=r.out, gate=gate)[0]
+        return gx, r.hand(s[:1] if one else s[:weight.numel()])
 
 
 def prelu(x, weight):
@@ -250,29 +249,23 @@ class BatchNormFn(torch.autograd.Function):
             return torch.empty_like(g), z, z.clone(), None, None, None, None, None, (g if has_res else None), None, None
         mean = mean.contiguous()                                         # the sums: sum dy, sum (x - mean)*dy
         # gamma's / beta's gradients go straight into the parameters' existing fp32 .grad buffers when they have them (the finalize
-        # step adds them there: what autograd's AccumulateGrad would do with one more launch each), else to autograd as tensors
-        wacc, wmode = _pass_slot(ctx.params[0], (c,), x.device) if ctx.needs_input_grad[1] else (None, None)
-        bacc, bmode = _pass_slot(ctx.params[1], (c,), x.device) if ctx.needs_input_grad[2] else (None, None)
-
-        def hand(mode, t, p):           # (a second use of the same module in this pass added into the first use's tensor: nothing to hand over)
-            if mode is None:
-                return None
-            if mode == "new+remember":
-                _remember_pass_grad(p, t)
-            return t
+        # step adds them there: what autograd's AccumulateGrad would do with one more launch each), or into the first use's tensor
+        # when the module runs twice in one pass, else to autograd as tensors
+        rw = route(ctx.params[0], (c,), x.device, accumulate=True, share=True, want=ctx.needs_input_grad[1])
+        rb = route(ctx.params[1], (c,), x.device, accumulate=True, share=True, want=ctx.needs_input_grad[2])
         if training:
             # dx = gamma*invstd * (dy - dbeta/M - xhat*dgamma/M),  xhat = (x - mean)*invstd
-            r = chan_reduce(x, g, 1, mean, 2, 5, M=M, creal=c, mean=mean, invstd=invstd.contiguous(), gamma=gamma.contiguous(), dgamma_acc=wacc, dbeta_acc=bacc)
+            r = chan_reduce(x, g, 1, mean, 2, 5, M=M, creal=c, mean=mean, invstd=invstd.contiguous(), gamma=gamma.contiguous(), dgamma_acc=rw.out, dbeta_acc=rb.out)
             dgamma, dbeta = r[0], r[1]
             gx = chan_apply(g, y=x, a=r[2], b=r[3], d=r[4])
         else:
-            r = chan_reduce(x, g, 1, mean, 3, 3, M=M, creal=c, invstd=invstd.contiguous(), gamma=gamma.contiguous(), dgamma_acc=wacc, dbeta_acc=bacc)
+            r = chan_reduce(x, g, 1, mean, 3, 3, M=M, creal=c, invstd=invstd.contiguous(), gamma=gamma.contiguous(), dgamma_acc=rw.out, dbeta_acc=rb.out)
             dgamma, dbeta = r[0], r[1]
             gx = chan_apply(g, a=r[2])
         gres = g if has_res else None
         if has_res and ctx.link is not None and ctx.link.armed:         # parked for the block's first conv (ResLink): its data-gradient launch adds it
             ctx.link.g, gres = g, None
-        return gx, hand(wmode, dgamma[:c], ctx.params[0]), hand(bmode, dbeta[:c], ctx.params[1]), None, None, None, None, None, gres, None, None
+        return gx, rw.hand(dgamma[:c]), rb.hand(dbeta[:c]), None, None, None, None, None, gres, None, None
 
 
 class BNPReLUFn(torch.autograd.Function):
@@ -314,23 +307,13 @@ class BNPReLUFn(torch.autograd.Function):
         g = g.contiguous()
 
         dev = x.device
-        wacc, wmode = _pass_slot(ctx.params[0], (c,), dev) if ctx.needs_input_grad[1] else (None, None)
-        bacc, bmode = _pass_slot(ctx.params[1], (c,), dev) if ctx.needs_input_grad[2] else (None, None)
-        sacc, smode = _pass_slot(ctx.params[2], tuple(ctx.params[2].shape), dev) if ctx.needs_input_grad[7] else (None, None)
+        rw = route(ctx.params[0], (c,), dev, accumulate=True, share=True, want=ctx.needs_input_grad[1])
+        rb = route(ctx.params[1], (c,), dev, accumulate=True, share=True, want=ctx.needs_input_grad[2])
+        rs = route(ctx.params[2], tuple(ctx.params[2].shape), dev, accumulate=True, share=True, want=ctx.needs_input_grad[7])
         r = chan_reduce(x, g, 3, mean.contiguous(), 2, 6, M=M, creal=c, mean=mean.contiguous(), invstd=invstd.contiguous(), gamma=gamma.contiguous(),
-                        dgamma_acc=wacc, dbeta_acc=bacc, bn_gate=(a.contiguous(), d.contiguous(), sl), total2=ns == 1, dslope_acc=sacc)
+                        dgamma_acc=rw.out, dbeta_acc=rb.out, bn_gate=(a.contiguous(), d.contiguous(), sl), total2=ns == 1, dslope_acc=rs.out)
         gx = chan_apply(g, y=x, z=x, a=r[2], b=r[3], d=r[4], slope=sl, gate_a=a.contiguous(), gate_d=d.contiguous())
-
-        def hand(mode, t, p):
-            if mode is None:
-                return None
-            if mode == "new+remember":
-                _remember_pass_grad(p, t)
-            return t
-        gw = hand(wmode, r[0][:c], ctx.params[0])
-        gb = hand(bmode, r[1][:c], ctx.params[1])
-        gs = hand(smode, r[5][:1] if ns == 1 else r[5][:ns], ctx.params[2])
-        return (gx, gw, gb, None, None, None, None, gs, None)
+        return (gx, rw.hand(r[0][:c]), rb.hand(r[1][:c]), None, None, None, None, rs.hand(r[5][:1] if ns == 1 else r[5][:ns]), None)
 
 
 _BN_PRELU_FUSED = _knob("SRK_NO_BN_PRELU", "0") != "1"      # A/B knob

@@ -5,7 +5,8 @@ import os
 import torch
 
 from . import _lib as L
-from .ops import _ADDR_LIMIT, _DT, _f32c, _grad_slot, _grad_target, _knob, _need_gpu, _pitch, _ptr, _stream, _tok, conv, pad16      # (ops.py imports this module at its END)
+from .grads import route
+from .ops import _ADDR_LIMIT, _DT, _f32c, _knob, _need_gpu, _pitch, _ptr, _stream, _tok, conv, pad16      # (ops.py imports this module at its END)
 from .ops_norm import chan_apply, chan_reduce, chan_sums
 from .packing import proj_groupable, proj_pack
 
@@ -149,11 +150,10 @@ class ProjFn(torch.autograd.Function):
         if sl is not None:                       # through the PReLU first: g <- g * (pre > 0 ? 1 : slope), slope gradient on the side
             if ctx.needs_input_grad[3]:
                 one = sl.numel() == 1
-                slot = _grad_slot(ctx.sparam, tuple(ctx.sparam.shape))
-                acc = slot[1] if (slot is not None and slot[0] == "acc") else None
+                r = route(ctx.sparam, tuple(ctx.sparam.shape), accumulate=True)
                 gp = torch.empty_like(g)
-                s = chan_reduce(pre, g, 2, None, 4, 1, total=one, creal=None if one else sl.numel(), dgamma_acc=acc, gate=(gp, sl))[0]
-                gs = None if acc is not None else (s[:1] if one else s[:sl.numel()])
+                s = chan_reduce(pre, g, 2, None, 4, 1, total=one, creal=None if one else sl.numel(), dgamma_acc=r.out, gate=(gp, sl))[0]
+                gs = r.hand(s[:1] if one else s[:sl.numel()])
                 g = gp
             else:
                 g = chan_apply(g, z=pre, slope=sl)
@@ -163,21 +163,15 @@ class ProjFn(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             xh, gl = (g, x) if up else (x, g)
             n, lh, lw, _ = gl.shape
-
-            def slot_of(p, shape):          # existing fp32 .grad: added into; GradSync's flat-buffer slice: written there; else fresh
-                sl_ = _grad_slot(p, shape)
-                acc_ = sl_[1] if (sl_ is not None and sl_[0] == "acc") else None
-                t = acc_ if acc_ is not None else _grad_target(p, shape, x.device)
-                return (t if t is not None else torch.empty(shape, dtype=torch.float32, device=x.device)), acc_ is not None
-            dw, wacc = slot_of(ctx.wparam, (32, 32, 8, 8))
-            db, bacc = slot_of(ctx.bparam, (32,)) if want_b else (None, False)
+            # existing fp32 .grad: added into; GradSync's flat-buffer slice: written there; else fresh
+            rw = route(ctx.wparam, (32, 32, 8, 8), x.device, accumulate=True, slice=True, buffer=True)
+            rb = route(ctx.bparam, (32,), x.device, accumulate=True, slice=True, buffer=True, want=want_b)
             scratch = torch.empty(L.load().srk_proj_wgrad_scratch_floats(n, lh, lw), dtype=torch.float32, device=x.device)
             L.call("srk_proj_wgrad", L.ProjWgradArgs(xh=xh.data_ptr(), xh_pitch=_pitch(xh), g=gl.data_ptr(), g_pitch=_pitch(gl),
-                                                     scratch=scratch.data_ptr(), dw=dw.data_ptr(), accumulate=int(wacc),
-                                                     N=n, H=lh, W=lw, dtype=_DT[x.dtype], db=_ptr(db), bias_side=2 if up else 1,
-                                                     db_accumulate=int(bacc)), _stream())
-            gw = None if wacc else dw
-            gb = None if (bacc or not want_b) else db
+                                                     scratch=scratch.data_ptr(), dw=rw.out.data_ptr(), accumulate=int(rw.acc),
+                                                     N=n, H=lh, W=lw, dtype=_DT[x.dtype], db=_ptr(rb.out), bias_side=2 if up else 1,
+                                                     db_accumulate=int(rb.acc)), _stream())
+            gw, gb = rw.hand(rw.out), rb.hand(rb.out)
         elif want_b:
             gb = chan_sums(g)[0][:32]
         return gx, gw, gb, gs, None

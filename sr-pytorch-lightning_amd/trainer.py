@@ -13,6 +13,8 @@ import torch
 import torch.distributed as dist
 from torch.nn.parallel import DistributedDataParallel as DDP
 
+from . import grads
+
 
 def dist_env():
     """(rank, world_size, local_rank) from the torchrun environment (1 process per GPU)."""
@@ -63,7 +65,7 @@ def unwrap_ddp(net):
     """Undo `wrap_ddp`'s process-wide switch once the wrapped model is done training."""
     from . import ops
     if isinstance(net, DDP):
-        ops.set_defer_wgrad(net.module.__dict__.pop("_srk_prev_defer", True))      # (SRK_NO_DEFER_WGRAD=1 stays off)
+        ops.set_defer_wgrad(net.module.__dict__.pop("_srk_prev_defer", True))
         return net.module
     return net
 
@@ -114,10 +116,10 @@ class GradSync:
                 cur[1] = off + n
                 cur[2].append(p)
                 off += n
-        # the HIP weight-gradient kernels write a parameter's gradient straight into its slice (ops._grad_target): what is left
+        # the HIP weight-gradient kernels write a parameter's gradient straight into its slice (grads.route): what is left
         # for `_pack_bucket` are the few gradients produced elsewhere (channel attention, PReLU, BatchNorm, torch ops)
         for p, v in self.views.items():
-            p.__dict__["_srk_grad_target"] = v
+            grads.set_slice(p, v)
         self._bucket_of = {p: i for i, b in enumerate(self.buckets) for p in b[2]}
         self._ready = [0] * len(self.buckets)
         self._next = 0                                   # first bucket not launched yet
@@ -127,21 +129,20 @@ class GradSync:
         if self.overlap and dist.is_initialized():
             for p in self.params:
                 self._hooks.append(p.register_post_accumulate_grad_hook(self._on_grad))
-                p.__dict__["_srk_flush_aware"] = True     # this hook flushes ops' deferred weight gradients before it reads them
+                grads.set_flush_aware(p, True)     # this hook flushes the deferred weight gradients before it reads them
 
     def remove_hooks(self):
         for h in self._hooks:
             h.remove()
         self._hooks = []
         for p in self.params:
-            p.__dict__.pop("_srk_flush_aware", None)
+            grads.set_flush_aware(p, False)
 
     def detach(self):
         """Undo everything this object attached to the parameters (hooks, gradient targets)."""
         self.remove_hooks()
         for p in self.params:
-            p.__dict__.pop("_srk_grad_target", None)
-            p.__dict__.pop("_srk_target_pass", None)
+            grads.forget(p)
 
     def broadcast(self):
         if self.world > 1:

@@ -138,7 +138,7 @@ def test_fused_batchnorm_prelu_vs_float64(A, dt, npar, shape):
 
 def test_shared_batchnorm_prelu_instance_used_twice_in_one_forward(A):
     """The reference's ResBlock appends the SAME BatchNorm2d / PReLU instance behind both of its convs (common.py:94-100; SRResNet):
-    the second use of a backward pass adds its [C]-sized gradients into the tensor the first use handed to autograd (ops._pass_slot).
+    the second use of a backward pass adds its [C]-sized gradients into the tensor the first use handed to autograd (grads.route, share=True).
     Against float64 torch, two passes in a row (the second with existing .grad buffers: accumulation)."""
     import torch.nn.functional as F
     from sr_amd import ops

@@ -158,7 +158,7 @@ def test_upload_small_roundtrip(A):
         assert torch.equal(dst[:n].cpu(), src) and int(dst[n:].sum()) == 0
 
 
-def test_channel_attention_gradients_are_summed_by_one_deferred_launch(A, monkeypatch):
+def test_channel_attention_row_sums_are_one_grouped_launch(A, monkeypatch):
     """RCAB backward: the per-sample slots of the conv_du gradients of every block are summed over the batch by ONE
     srk_rowsum_group launch when the pass ends; a second pass accumulates into the existing .grad through autograd
     (immediate sums), and a module applied twice in one pass is handled."""
@@ -184,7 +184,7 @@ def test_channel_attention_gradients_are_summed_by_one_deferred_launch(A, monkey
 
     calls = []
     lib = A._lib.load()
-    monkeypatch.setattr(A.ops, "_launch_rowsums", (lambda f: (lambda rj, st: (calls.append(len(rj)), f(rj, st))[1]))(A.ops._launch_rowsums))
+    monkeypatch.setattr(A.grads, "_launch_rowsums", (lambda f: (lambda rj, st: (calls.append(len(rj)), f(rj, st))[1]))(A.grads._launch_rowsums))
     run([0, 1, 2])
     assert calls == [3], "one launch for the three blocks"
     g1 = ca_grads()
