@@ -14,9 +14,13 @@ models/srmodel.py:145-171).  `value` = LR patches/s over all ranks with inputs r
 `--steps K` is the number of timed steps and `ms_per_step` the time of one of them.  `--dump-outputs DIR` writes what the last
 timed step computed to DIR/*.npy (dump_outputs), so that two builds run with the same arguments can be compared output for output.
 
-Rank 0 prints ONE JSON line.  Extra objects: `roofline` (the dominant kernel, the 64->64 3x3 implicit-GEMM
-conv, timed with HIP events on its own stream inside this process) and, at N=1, `cpu_baseline` (the CPU
-oracle's training step timed on this host's cores over a bounded sample).
+Rank 0 prints ONE JSON line.  A plain run does only what the headline figure needs: set up, warm up, time the K steps,
+dump if asked, print.  `--full` adds the measurements that take runs of their own, all after the timed steps:
+`sustained_ms_per_step` (--sustain-seconds of further steps), `roofline` (the dominant kernel, the 64->64 3x3
+implicit-GEMM conv, timed with HIP events on its own stream inside this process), at N=1 `other_configs` /
+`layerwise_hr_stage` (the other BASELINE configurations at batch 16) and `cpu_baseline` (the CPU oracle's training
+step timed on this host's cores over a bounded sample, with the parity checks against it), and with several ranks
+`config.allreduce_ms`.  --no-roofline / --no-other-configs / --no-cpu-baseline drop one of them from a --full run.
 """
 import argparse
 import contextlib
@@ -61,18 +65,25 @@ def parse():
     p.add_argument("--patch", type=int, default=48, help="LR patch edge")
     p.add_argument("--scale", type=int, default=4)
     p.add_argument("--no-graph", action="store_true", help="eager launches instead of one hipGraph per step")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps, also run the sustained window, the roofline, the other configurations, the CPU baseline "
+                        "and (several ranks) the all-reduce timing; without it only the headline figure is measured")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and its parity checks")
     p.add_argument("--inference", action="store_true", help="forward only (patches/s of SRModel.forward)")
-    p.add_argument("--sustain-seconds", type=float, default=2.0,
-                   help="after the timed steps, keep stepping this long and report sustained_ms_per_step (0 = skip)")
-    p.add_argument("--no-roofline", action="store_true")
+    p.add_argument("--sustain-seconds", type=float, default=None,
+                   help="with --full: after the timed steps, keep stepping this long and report sustained_ms_per_step (default 2, 0 = skip)")
+    p.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline")
     p.add_argument("--no-other-configs", action="store_true",
-                   help="skip the batch-16 runs of the five BASELINE models that follow the timed region of the default line")
+                   help="with --full: skip the batch-16 runs of the five BASELINE models that follow the timed region of the default line")
     p.add_argument("--dump-outputs", metavar="DIR",
                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all; see dump_outputs)")
     a = p.parse_args()
     if a.steps < 1 or a.warmup < 0:
         p.error("--steps must be >= 1 and --warmup >= 0")
+    if a.sustain_seconds is None:
+        a.sustain_seconds = 2.0 if a.full else 0.0
+    elif a.sustain_seconds > 0 and not a.full:
+        p.error("--sustain-seconds above 0 needs --full")
     return a
 
 
@@ -999,7 +1010,7 @@ def main():
     # the collective alone (all buckets back to back, every rank), HIP events on the launch stream: what a step exposes when nothing
     # overlaps it -- so that the first multi-GPU run explains itself (`config.allreduce_ms`, `config.rccl_ranks`)
     ar_ms, ar_sync = None, (ogs.gsync if (ogs is not None and ogs.gsync is not None) else gsync)
-    if ddp and ar_sync is not None and ar_sync.flat is not None:
+    if a.full and ddp and ar_sync is not None and ar_sync.flat is not None:
         torch.cuda.synchronize()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         for _ in range(3):
@@ -1049,7 +1060,7 @@ def main():
         if sustained is not None:
             out["sustained_ms_per_step"] = round(sustained * 1e3, 4)
             out["sustained_value"] = round(a.batch * world / sustained, 2)
-        if not a.no_roofline:
+        if a.full and not a.no_roofline:
             try:
                 # (several ranks: rank 0 alone must not run a backward pass through a model whose gradient hooks / flat buffer belong to the
                 # process group -- a hook-launched all-reduce on one rank would wait for the others forever; the N = 1 line carries `in_step`)
@@ -1057,7 +1068,7 @@ def main():
                 out["roofline"] = dominant_kernel_roofline(A, a.model, a.batch, a.patch, feats, a.dtype, in_step=ins)
             except Exception as e:  # noqa: BLE001
                 out["roofline"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and not a.no_other_configs and not a.inference and a.model == "edsr_baseline" and a.batch == 256:
+        if a.full and world == 1 and not a.no_other_configs and not a.inference and a.model == "edsr_baseline" and a.batch == 256:
             # BASELINE.json configs 2-5 (+ SURVEY 8(f)'s SRResNet / D-DBPN) at the reference's batch (16 patches per GPU), a few seconds each, after the timed region
             oc = []
             graphs = None                      # (frees the default line's graph and its private memory pool)
@@ -1104,7 +1115,7 @@ def main():
                 finally:
                     A.ops._HR_COLLAPSE = True
                 torch.cuda.empty_cache()
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(a.model, a.scale, a.patch, model=model, lr=batch["lr"], hr=batch["hr"])
             except Exception as e:  # noqa: BLE001

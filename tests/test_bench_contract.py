@@ -16,6 +16,16 @@ def test_flags_exist():
         assert flag in out.stdout
 
 
+def test_full_is_an_option_and_the_sustained_window_needs_it():
+    """A plain run measures the headline figure only; --sustain-seconds asks for a --full leg and is refused without --full
+    rather than ignored."""
+    bench = os.path.join(ROOT, "bench.py")
+    out = subprocess.run([sys.executable, bench, "--help"], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and "--full" in out.stdout
+    out = subprocess.run([sys.executable, bench, "--sustain-seconds", "1"], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 2 and "--full" in out.stderr
+
+
 def test_steps_must_be_positive():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=300)
     assert out.returncode == 2 and "--steps" in out.stderr

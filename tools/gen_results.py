@@ -79,7 +79,7 @@ def block(tag, short=False):
     d = _load(f"{tag}_bench_default.json")
     if d:
         c, r = d["config"], d.get("roofline", {})
-        out.append(f"**Default line** (`profiles/{tag}_bench_default.json`, `python bench.py`): **{d['value']:,.0f} LR patches/s**, {d['ms_per_step']:.3f} ms per step "
+        out.append(f"**Default line** (`profiles/{tag}_bench_default.json`, `python bench.py --full`): **{d['value']:,.0f} LR patches/s**, {d['ms_per_step']:.3f} ms per step "
                    f"(sustained {d.get('sustained_value', 0):,.0f}); `model_mfma_frac` {d['model_mfma_frac']:.4f} on the reference graph's {c['gflop_per_patch']['reference_graph']} GFLOP per patch, "
                    f"{d['model_mfma_frac_executed']:.4f} on the {c['gflop_per_patch']['executed']} GFLOP the path executes; HR stage: {c['hr_stage'].split(':')[0]}.")
         lw = d.get("layerwise_hr_stage")
