@@ -528,6 +528,31 @@ typedef struct srk_ssim_args {
 } srk_ssim_args;
 int srk_image_ssim(const srk_ssim_args* a, srk_stream_t stream);
 
+/* ---- MS-SSIM with piq.multi_scale_ssim's defaults (reference configs/train_default_sr.yml `metrics`), csrc/ms_ssim.hip -----------
+ * Five levels; level 0 is the input, level k > 0 is level k-1 replicate-padded by p = max(H % 2, W % 2) pixels on the top and
+ * left only, then 2x2 / stride-2 average-pooled (floor).  No initial average-pool.  Per level and (image, channel) plane the SSIM
+ * and contrast-structure maps (separable 11-tap Gaussian, sigma) are averaged over the valid region ((Hk-10) x (Wk-10));
+ * v = prod_{k<4} relu(cs_k)^w_k * relu(ss_4)^w_4, and *out = the mean of v over channels and images.  H, W >= 161.
+ * Inputs are used as given (the model clamps before its metrics).  fp32 NCHW planar.  No host sync, no float atomics.
+ * workspace: srk_ms_ssim_workspace_bytes(N, C, H, W) bytes (levels 1-4 of both images);
+ * partials: [N*C][srk_ms_ssim_tiles(H, W)][2] doubles, 16-byte aligned: per 16x16 map tile (sum ss, sum cs); the tiles of
+ * level k of a plane are [first[k], first[k+1]).  ------------------------------------------------------------------------------ */
+typedef struct srk_ms_ssim_args {
+  const float* x;                         /* [N][C][H][W]                                                   */
+  const float* y;
+  float* workspace;
+  double* partials;
+  float* out;                             /* device scalar                                                  */
+  int N, C, H, W;
+  float sigma, k1, k2;                    /* 1.5, 0.01, 0.03                                                */
+  float w0, w1, w2, w3, w4;               /* 0.0448, 0.2856, 0.3001, 0.2363, 0.1333                        */
+} srk_ms_ssim_args;
+/* bytes of the pyramid workspace (a multiple of 256), or -1 when the sizes are refused */
+long long srk_ms_ssim_workspace_bytes(int N, int C, int H, int W);
+/* map tiles per plane over all five levels (-1 when refused); first (nullable) receives the 6 level boundaries */
+int srk_ms_ssim_tiles(int H, int W, int* first);
+int srk_ms_ssim(const srk_ms_ssim_args* a, srk_stream_t stream);
+
 /* ---- remaining conv models: SRResNet and DDBPN ---------------------------------------------------
  * im2col / col2im on NHWC tensors for any kernel size K, stride and zero padding:
  *   cols[n][oy][ox][(kh*K + kw)*C + c] = x[n][oy*stride + kh - pad][ox*stride + kw - pad][c]          (srk_unfold_nhwc)

@@ -186,6 +186,11 @@ class SsimArgs(C.Structure):
                 ("sigma", _f), ("k1", _f), ("k2", _f), ("sums", _p)]
 
 
+class MsSsimArgs(C.Structure):
+    _fields_ = [("x", _p), ("y", _p), ("workspace", _p), ("partials", _p), ("out", _p), ("N", _i), ("C", _i), ("H", _i), ("W", _i),
+                ("sigma", _f), ("k1", _f), ("k2", _f), ("w0", _f), ("w1", _f), ("w2", _f), ("w3", _f), ("w4", _f)]
+
+
 class L1Args(C.Structure):
     _fields_ = [("sr", _p), ("hr", _p), ("n", C.c_longlong), ("sign", _p), ("partial", _p), ("gout", _p),
                 ("scale", _f), ("grad", _p)]
@@ -251,6 +256,7 @@ LAUNCHERS = {
     "srk_sample_patches": PatchArgs,
     "srk_image_sse": SseArgs,
     "srk_image_ssim": SsimArgs,
+    "srk_ms_ssim": MsSsimArgs,
     "srk_l1_loss_fwd": L1Args,
     "srk_l1_loss_bwd": L1Args,
     "srk_flip_fwd": FlipArgs,
@@ -274,7 +280,8 @@ OTHER_SYMBOLS = ("srk_conv_tile", "srk_last_error", "srk_version", "srk_device_c
                  "srk_conv_pair_tiles", "srk_rowsum_group", "srk_pw_shape_ok", "srk_pw_pack_bytes", "srk_pw_pack_group", "srk_weight_norm_group", "srk_pw_wgrad_ranges", "srk_l1_loss_mean", "srk_chan_stats_finalize", "srk_pack_group_tiles", "srk_pack_conv_weights_group_tiled",
                  "srk_proj_pack", "srk_proj_pack_bytes", "srk_proj_wgrad_scratch_floats", "srk_proj_pack_group", "srk_wgrad_slab_cout",
                  "srk_hrtail_scratch_floats", "srk_adam_step_scaled", "srk_adam_check_scaled", "srk_adam_update_scaled", "srk_loss_scale_update", "srk_conv_bits_ok",
-                 "srk_conv_trunk", "srk_conv_trunk_ok", "srk_flip_blocks", "srk_flip_mean")
+                 "srk_conv_trunk", "srk_conv_trunk_ok", "srk_flip_blocks", "srk_flip_mean",
+                 "srk_ms_ssim_workspace_bytes", "srk_ms_ssim_tiles")
 
 _lib = None
 
@@ -359,6 +366,11 @@ def load():
         lib.srk_flip_blocks.argtypes = [C.c_int, C.c_int, C.c_int]
         lib.srk_flip_blocks.restype = C.c_int
     lib.srk_l1_blocks.restype = C.c_int
+    if not isinstance(getattr(lib, "srk_ms_ssim_tiles", None), _Absent):
+        lib.srk_ms_ssim_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+        lib.srk_ms_ssim_workspace_bytes.restype = C.c_longlong
+        lib.srk_ms_ssim_tiles.argtypes = [C.c_int, C.c_int, C.c_void_p]
+        lib.srk_ms_ssim_tiles.restype = C.c_int
     lib.srk_pw_shape_ok.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.srk_pw_shape_ok.restype = C.c_int
     lib.srk_pw_pack_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]

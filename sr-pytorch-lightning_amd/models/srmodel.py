@@ -117,6 +117,46 @@ def _ssim(x, y, kernel_size=11, sigma=1.5, k1=0.01, k2=0.03):
     return ss.mean(dim=(-1, -2)).mean(dim=1).mean()
 
 
+def _ms_ssim(x, y, kernel_size=11, sigma=1.5, k1=0.01, k2=0.03):
+    """MS-SSIM with piq.multi_scale_ssim's defaults (5 levels, scale weights 0.0448 ... 0.1333, no initial avg-pool; level k is level
+    k-1 replicate-padded by max(H % 2, W % 2) on the top and left, then 2x2 average-pooled).  On the GPU: srk_ms_ssim."""
+    if x.is_cuda and kernel_size == 11:
+        from .. import ops
+        return ops.ms_ssim(x, y, sigma=sigma, k1=k1, k2=k2)
+    return _ms_ssim_torch(x, y, kernel_size, sigma, k1, k2)
+
+
+def _ms_ssim_torch(x, y, kernel_size=11, sigma=1.5, k1=0.01, k2=0.03):
+    """The plain-torch fp32 form of _ms_ssim (the CPU path; tools/microbench_ms_ssim.py also times it on the GPU)."""
+    from ..ops_metrics import MS_SSIM_WEIGHTS, ms_ssim_check
+    ms_ssim_check(x, y)
+    x, y = x.float(), y.float()
+    c = x.shape[1]
+    co = torch.arange(kernel_size, dtype=torch.float32, device=x.device) - (kernel_size - 1) / 2.0
+    g = torch.exp(-(co ** 2) / (2 * sigma ** 2))
+    g = g / g.sum()
+    k = torch.outer(g, g).view(1, 1, kernel_size, kernel_size).repeat(c, 1, 1, 1)
+    c1, c2 = k1 ** 2, k2 ** 2
+    v = 1.0
+    for level, wt in enumerate(MS_SSIM_WEIGHTS):
+        if level > 0:
+            p = max(x.shape[-2] % 2, x.shape[-1] % 2)
+            x = F.avg_pool2d(F.pad(x, [p, 0, p, 0], mode="replicate"), 2)
+            y = F.avg_pool2d(F.pad(y, [p, 0, p, 0], mode="replicate"), 2)
+        # moments of the images shifted by their plane means: the variances lose no digits to cancellation in fp32
+        kx, ky = x.mean(dim=(-1, -2), keepdim=True), y.mean(dim=(-1, -2), keepdim=True)
+        xs, ys = x - kx, y - ky
+        mx, my = F.conv2d(xs, k, groups=c), F.conv2d(ys, k, groups=c)
+        sxx = F.conv2d(xs * xs, k, groups=c) - mx ** 2
+        syy = F.conv2d(ys * ys, k, groups=c) - my ** 2
+        sxy = F.conv2d(xs * ys, k, groups=c) - mx * my
+        mx, my = mx + kx, my + ky
+        cs = (2 * sxy + c2) / (sxx + syy + c2)
+        m = cs if level < len(MS_SSIM_WEIGHTS) - 1 else (2 * mx * my + c1) / (mx ** 2 + my ** 2 + c1) * cs
+        v = v * torch.relu(m.mean(dim=(-1, -2))) ** wt
+    return v.mean(dim=1).mean()
+
+
 def _psnr_y(x, y, shave):
     """PSNR on BT.601 luma with a `shave`-pixel border removed (the SR community convention)."""
     def lum(t):
@@ -142,7 +182,8 @@ def _flip_metric(x, y):
     return flip.flip(x, y)
 
 
-_supported_metrics = {"PSNR": _psnr, "SSIM": _ssim, "PSNR-Y": _psnr_y_metric, "FLIP": _flip_metric}   # srmodel.py:47-54 (+ PSNR-Y)
+_supported_metrics = {"PSNR": _psnr, "SSIM": _ssim, "PSNR-Y": _psnr_y_metric, "FLIP": _flip_metric,   # srmodel.py:47-54 (+ PSNR-Y)
+                      "MS-SSIM": _ms_ssim}
 
 
 def _dtype_from_precision(precision):
@@ -368,7 +409,7 @@ class SRModel(_Base):
         for metric in metrics:
             if metric in _supported_metrics:
                 used.append((metric, _supported_metrics[metric]))
-            elif metric in {'BRISQUE', 'LPIPS', 'MS-SSIM'}:
+            elif metric in {'BRISQUE', 'LPIPS'}:
                 raise NotImplementedError(f'metric {metric} needs piq and is outside this build. Supported: {", ".join(_supported_metrics)}')
             else:
                 raise AttributeError(f'Couldn\'t find metric {metric}. Supported metrics: {", ".join(_supported_metrics)}')

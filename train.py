@@ -29,7 +29,7 @@ def parse(argv=None):
     p.add_argument("--batch_size", type=int, default=16)
     p.add_argument("--precision", default="bf16", help="32, 16 or bf16 (Trainer key of the reference)")
     p.add_argument("--losses", default="l1")
-    p.add_argument("--metrics", nargs="+", default=None, help="validation metrics (default: the model's, PSNR SSIM); e.g. PSNR SSIM FLIP")
+    p.add_argument("--metrics", nargs="+", default=None, help="validation metrics (default: the model's, PSNR SSIM); e.g. PSNR SSIM MS-SSIM FLIP")
     p.add_argument("--optimizer", default="ADAM")
     p.add_argument("--max_steps", type=int, default=100)
     p.add_argument("--max_epochs", type=int, default=-1)
