@@ -513,6 +513,36 @@ int srk_flip_bwd(const srk_flip_args* a, srk_stream_t stream);
 /* *out = (partial[0] + ... + partial[nb-1]) / n (the forward's partial sums -> the mean error), one launch */
 int srk_flip_mean(const double* partial, int nb, long long n, float* out, srk_stream_t stream);
 
+/* ---- HaarPSI loss (piq 0.7.0 HaarPSILoss with its defaults; reference srmodel.py:36), csrc/haarpsi.hip ------------------------
+ * x = clamp(sr, 0, 1) (test), y = hr (reference), both x255; C == 3: YIQ per pixel, C == 1: the channel is Y.  Subsampled by a
+ * bottom / right zero pad of p = max(H % 2, W % 2) and a 2x2 / stride-2 mean (H' = (H + p) / 2, W' = (W + p) / 2).  Haar
+ * coefficients of Y' at k = 2, 4, 8 (zero pad k/2 - 1 top / left, k/2 bottom / right), weights w_o = max(|h_8^o x|, |h_8^o y|),
+ * similarities sim_o = (S(h_2^o) + S(h_4^o)) / 2, S(u, v) = (2uv + 30) / (u^2 + v^2 + 30 + 2^-23) on magnitudes; for C == 3 also
+ * the I / Q term on a bottom / right padded 2x2 / stride-1 mean, with w_2 = (w_0 + w_1) / 2.  Per image
+ * r_n = (sum sigma(4.2 sim) w + eps) / (sum w + eps), eps = 2^-23; h_n = (logit(r_n) / 4.2)^2; loss = 1 - mean h_n.
+ * Forward: one workgroup per (image, 16x16 half-res tile) -> two doubles per tile (fixed slots, no atomics).  Finalize: one
+ * workgroup, fixed-order fp64 sums -> loss, index and per-image factors.  Backward: recomputes the tile on a 7-pixel halo from
+ * the subsampled planes the forward kept; d loss / d sr times *gout (device scalar: no host sync), zero where sr lies outside
+ * [0, 1].  hr gets no gradient and is not range-checked.  NCHW fp32, C in {1, 3}, H, W >= 16, N <= 65535. ---------------------------------------------------------- */
+typedef struct srk_haarpsi_args {
+  const float* sr;                        /* test image [N][C][H][W] (forward, backward; clamped on load)                    */
+  const float* hr;                        /* reference image [N][C][H][W] (forward)                                          */
+  int N, C, H, W;
+  double* partial;                        /* [srk_haarpsi_tiles(N, H, W)][2]: per tile sum sigma(alpha sim) w, sum w        */
+  float* planes;                          /* forward writes (optional), backward reads: [N][C == 3 ? 6 : 2][H'][W'] Y'x, Y'y  */
+                                          /* (and I'x, Q'x, I'y, Q'y): the subsampled x255 planes of both images            */
+  float* stats;                           /* [N][4]: r_n, 1 / (W_n + eps), d loss / d r_n for a unit upstream gradient, h_n  */
+  float* loss;                            /* finalize: device scalar 1 - index                                               */
+  float* index;                           /* finalize, optional: device scalar mean h_n                                      */
+  const float* gout;                      /* backward: device scalar                                                         */
+  float* grad;                            /* backward: [N][C][H][W] d loss / d sr                                            */
+} srk_haarpsi_args;
+/* forward tiles over the whole batch (N x per-image tiles), or -1 when the sizes are refused (H or W < 16) */
+int srk_haarpsi_tiles(int N, int H, int W);
+int srk_haarpsi_fwd(const srk_haarpsi_args* a, srk_stream_t stream);
+int srk_haarpsi_finalize(const srk_haarpsi_args* a, srk_stream_t stream);
+int srk_haarpsi_bwd(const srk_haarpsi_args* a, srk_stream_t stream);
+
 /* ---- SSIM with piq.ssim's defaults (reference srmodel.py:52-53,567-593 -> piq.ssim): images are average-pooled by
  * `pool` = max(1, round(min(H, W) / 256)) (floor division of the extent, as F.avg_pool2d), filtered with the separable
  * 11-tap Gaussian (sigma), and the SSIM map of the VALID region ((Hp-10) x (Wp-10)) is summed per (image, channel)

@@ -201,6 +201,11 @@ class FlipArgs(C.Structure):
                 ("gout", _p), ("scale", _f), ("grad", _p)]
 
 
+class HaarpsiArgs(C.Structure):
+    _fields_ = [("sr", _p), ("hr", _p), ("N", _i), ("C", _i), ("H", _i), ("W", _i), ("partial", _p), ("planes", _p), ("stats", _p), ("loss", _p),
+                ("index", _p), ("gout", _p), ("grad", _p)]
+
+
 class UnfoldNhwcArgs(C.Structure):
     _fields_ = [("x", _p), ("x_pitch", _i), ("x_coff", _i), ("cols", _p), ("cols_pitch", _i),
                 ("N", _i), ("H", _i), ("W", _i), ("C", _i), ("K", _i), ("stride", _i), ("pad", _i), ("Ho", _i), ("Wo", _i), ("dtype", _i)]
@@ -261,6 +266,9 @@ LAUNCHERS = {
     "srk_l1_loss_bwd": L1Args,
     "srk_flip_fwd": FlipArgs,
     "srk_flip_bwd": FlipArgs,
+    "srk_haarpsi_fwd": HaarpsiArgs,
+    "srk_haarpsi_finalize": HaarpsiArgs,
+    "srk_haarpsi_bwd": HaarpsiArgs,
     "srk_unfold_nhwc": UnfoldNhwcArgs,
     "srk_fold_nhwc": FoldNhwcArgs,
     "srk_chan_stats": ChanStatsArgs,
@@ -281,7 +289,7 @@ OTHER_SYMBOLS = ("srk_conv_tile", "srk_last_error", "srk_version", "srk_device_c
                  "srk_proj_pack", "srk_proj_pack_bytes", "srk_proj_wgrad_scratch_floats", "srk_proj_pack_group", "srk_wgrad_slab_cout",
                  "srk_hrtail_scratch_floats", "srk_adam_step_scaled", "srk_adam_check_scaled", "srk_adam_update_scaled", "srk_loss_scale_update", "srk_conv_bits_ok",
                  "srk_conv_trunk", "srk_conv_trunk_ok", "srk_flip_blocks", "srk_flip_mean",
-                 "srk_ms_ssim_workspace_bytes", "srk_ms_ssim_tiles")
+                 "srk_ms_ssim_workspace_bytes", "srk_ms_ssim_tiles", "srk_haarpsi_tiles")
 
 _lib = None
 
@@ -371,6 +379,9 @@ def load():
         lib.srk_ms_ssim_workspace_bytes.restype = C.c_longlong
         lib.srk_ms_ssim_tiles.argtypes = [C.c_int, C.c_int, C.c_void_p]
         lib.srk_ms_ssim_tiles.restype = C.c_int
+    if not isinstance(getattr(lib, "srk_haarpsi_tiles", None), _Absent):
+        lib.srk_haarpsi_tiles.argtypes = [C.c_int, C.c_int, C.c_int]
+        lib.srk_haarpsi_tiles.restype = C.c_int
     lib.srk_pw_shape_ok.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.srk_pw_shape_ok.restype = C.c_int
     lib.srk_pw_pack_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]

@@ -73,8 +73,16 @@ def _flip_loss(sr, hr):
     return flip.flip_loss(sr, hr)
 
 
-_supported_losses = {"l1": _l1_loss, "l2": F.mse_loss, "mae": _l1_loss, "mse": F.mse_loss, "flip": _flip_loss}
-_out_of_scope_losses = {"adaptive", "dists", "edge_loss", "haarpsi", "lpips", "pencil_sketch", "pieapp"}
+def _haarpsi_loss(sr, hr):
+    """piq.HaarPSILoss (srmodel.py:36), called as the reference does on clamp(sr, 0, 1) and hr (srmodel.py:525-528): 1 - HaarPSI;
+    on the GPU the fused HIP forward/backward (haarpsi.HaarPSILossFn, which clamps inside), elsewhere haarpsi.haarpsi_torch."""
+    from .. import haarpsi
+    return haarpsi.haarpsi_loss(sr, hr)
+
+
+_supported_losses = {"l1": _l1_loss, "l2": F.mse_loss, "mae": _l1_loss, "mse": F.mse_loss, "flip": _flip_loss,
+                     "haarpsi": _haarpsi_loss}
+_out_of_scope_losses = {"adaptive", "dists", "edge_loss", "lpips", "pencil_sketch", "pieapp"}
 
 # models/srmodel.py:57-64
 # 'ADAM' is torch.optim.Adam with the update of GPU parameters as one HIP launch (sr-pytorch-lightning_amd/optim.py)

@@ -1507,3 +1507,4 @@ from .ops_proj import *      # noqa: E402,F401,F403  unfold / fold, projection a
 from .ops_proj import _proj_launch      # noqa: E402,F401  (bench.py / tools/microbench_proj.py time the raw launches)
 from .ops_metrics import *   # noqa: E402,F401,F403  PSNR / SSIM reductions, L1 loss
 from .flip import *          # noqa: E402,F401,F403  FLIP loss and metric (csrc/flip.hip)
+from .haarpsi import *       # noqa: E402,F401,F403  HaarPSI loss (csrc/haarpsi.hip)
