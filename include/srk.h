@@ -812,6 +812,29 @@ int srk_adam_check_scaled(const srk_adam_args* a, float* scaler_state, srk_strea
 int srk_adam_update_scaled(const srk_adam_args* a, const float* scaler_state, srk_stream_t stream);
 int srk_loss_scale_update(float* scaler_state, srk_stream_t stream);
 
+/* ---- optimizer: Ranger (torch_optimizer 0.3.0 `Ranger`: RAdam + Lookahead) over the same table ---------------------------
+ * The models' `optimizer="Ranger"` (reference models/srmodel.py:57-64).  The tensors and blocks are srk_adam_slot / srk_adam_block;
+ * `m`, `v`, `slow` are the flat exp_avg / exp_avg_sq / slow_buffer of all tensors (tensor i at `state_off`).  Per tensor:
+ *     t = steps[step_idx] + 1;  v = b2*v + (1-b2)*g*g;  m = b1*m + (1-b1)*g;
+ *     N_max = 2/(1-b2) - 1;  b2t = b2^t;  N = N_max - 2*t*b2t/(1-b2t)
+ *     s = N > n_sma_threshold ? sqrt((1-b2t)*(N-4)/(N_max-4)*(N-2)/N*N_max/(N_max-2)) / (1-b1^t) : 1/(1-b1^t)
+ *     p += (-weight_decay*lr) * p   (weight_decay != 0);   p += (-s*lr) * (N > thr ? m/(sqrt(v)+eps) : m)
+ *     t == 1: slow = p (before the update);   t % k == 0: slow += alpha*(p - slow); p = slow
+ * N and s are computed in DOUBLE from the double hyper-parameters below (N cancels catastrophically at small t); -s*lr and
+ * -weight_decay*lr are rounded to fp32 once; the element arithmetic is fp32.  Step counts advance as srk_adam_step's do.
+ * srk_ranger_step_scaled / _check_scaled / _update_scaled: srk_adam_*'s loss-scaling contract (then srk_loss_scale_update). */
+typedef struct {
+  const srk_adam_slot* slots; const srk_adam_block* blocks; int nslots, nblocks;
+  float* m; float* v; float* slow;
+  float* steps;
+  double lr, beta1, beta2, alpha, n_sma_threshold, eps, weight_decay;
+  int k;
+} srk_ranger_args;
+int srk_ranger_step(const srk_ranger_args* a, srk_stream_t stream);
+int srk_ranger_step_scaled(const srk_ranger_args* a, float* scaler_state, srk_stream_t stream);
+int srk_ranger_check_scaled(const srk_ranger_args* a, float* scaler_state, srk_stream_t stream);
+int srk_ranger_update_scaled(const srk_ranger_args* a, const float* scaler_state, srk_stream_t stream);
+
 /* ---- misc ------------------------------------------------------------------------------------------ */
 const char* srk_last_error(void);
 int srk_version(void);

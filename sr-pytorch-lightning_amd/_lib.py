@@ -107,6 +107,12 @@ class AdamArgs(C.Structure):
                 ("one_minus_beta1", _f), ("one_minus_beta2", _f)]
 
 
+class RangerArgs(C.Structure):
+    _fields_ = [("slots", _p), ("blocks", _p), ("nslots", _i), ("nblocks", _i), ("m", _p), ("v", _p), ("slow", _p), ("steps", _p),
+                ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("alpha", C.c_double),
+                ("n_sma_threshold", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double), ("k", _i)]
+
+
 class WgradArgs(C.Structure):
     _fields_ = [("x", _p), ("x_pitch", _i), ("x_coff", _i), ("x_ps", _i),
                 ("dy", _p), ("dy_pitch", _i), ("dy_coff", _i), ("dy_ps", _i),
@@ -249,6 +255,7 @@ LAUNCHERS = {
     "srk_pw_backward": PwBwdArgs,
     "srk_pw_wgrad": PwWgradArgs,
     "srk_adam_step": AdamArgs,
+    "srk_ranger_step": RangerArgs,
     "srk_chan_finalize": ChanFinalizeArgs,
     "srk_conv2d_wgrad": WgradArgs,
     "srk_wgrad_finalize": WgradFinArgs,
@@ -288,6 +295,7 @@ OTHER_SYMBOLS = ("srk_conv_tile", "srk_last_error", "srk_version", "srk_device_c
                  "srk_conv_pair_tiles", "srk_rowsum_group", "srk_pw_shape_ok", "srk_pw_pack_bytes", "srk_pw_pack_group", "srk_weight_norm_group", "srk_pw_wgrad_ranges", "srk_l1_loss_mean", "srk_chan_stats_finalize", "srk_pack_group_tiles", "srk_pack_conv_weights_group_tiled",
                  "srk_proj_pack", "srk_proj_pack_bytes", "srk_proj_wgrad_scratch_floats", "srk_proj_pack_group", "srk_wgrad_slab_cout",
                  "srk_hrtail_scratch_floats", "srk_adam_step_scaled", "srk_adam_check_scaled", "srk_adam_update_scaled", "srk_loss_scale_update", "srk_conv_bits_ok",
+                 "srk_ranger_step_scaled", "srk_ranger_check_scaled", "srk_ranger_update_scaled",
                  "srk_conv_trunk", "srk_conv_trunk_ok", "srk_flip_blocks", "srk_flip_mean",
                  "srk_ms_ssim_workspace_bytes", "srk_ms_ssim_tiles", "srk_haarpsi_tiles")
 
@@ -412,6 +420,10 @@ def load():
     for fn in (lib.srk_adam_check_scaled, lib.srk_adam_update_scaled):
         fn.argtypes = [C.POINTER(AdamArgs), C.c_void_p, C.c_void_p]
         fn.restype = C.c_int
+    if not isinstance(getattr(lib, "srk_ranger_step_scaled", None), _Absent):
+        for fn in (lib.srk_ranger_step_scaled, lib.srk_ranger_check_scaled, lib.srk_ranger_update_scaled):
+            fn.argtypes = [C.POINTER(RangerArgs), C.c_void_p, C.c_void_p]
+            fn.restype = C.c_int
     lib.srk_loss_scale_update.argtypes = [C.c_void_p, C.c_void_p]
     lib.srk_loss_scale_update.restype = C.c_int
     lib.srk_last_error.restype = C.c_char_p

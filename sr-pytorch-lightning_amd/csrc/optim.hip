@@ -122,6 +122,128 @@ __global__ __launch_bounds__(ADAM_NT) void adam_bump_kernel(const srk_adam_args 
   for (int i = blockIdx.x * ADAM_NT + threadIdx.x; i < a.nslots; i += gridDim.x * ADAM_NT) a.steps[a.slots[i].step_idx] += 1.f;
 }
 
+
+// ---- Ranger (torch_optimizer 0.3.0 `Ranger` = RAdam + Lookahead) over the same table ---------------------------------------
+// Per tensor, t = its step count after this step (srk.h has the rule).  The branches -- rectified or not (N_sma > threshold) and
+// the Lookahead sync (t % k == 0) -- are decided HERE from the device count, so a replayed hipGraph takes the branch of the
+// step it replays, not the one of the step it was captured at.  N_sma and the step size are formed in DOUBLE from double
+// hyper-parameters (N_sma cancels: 1999 - 1993.0 at t = 6, so fp32 scalars are off by 0.57 %), then -s*lr is rounded to fp32
+// once, as torch rounds a Python scalar; the per-element arithmetic is fp32 in the package's order.
+// Traffic: p, m, v read + written, g read = 28 B per parameter; a sync step adds the slow buffer (36 B).  Both branches are
+// uniform per block (one tensor per block), so the slow buffer is touched only on sync steps and at t = 1 (slow = p).
+
+// the element arithmetic of one block, with the block-uniform decisions made
+struct RangerBlock {
+  float* p; const float* g; float* m; float* v; float* slow;
+  long long e0, e1;
+  float inv_scale, step, decay, b1, b2, omb1, omb2, eps, alpha;
+  bool wd, rect, sync, first;
+};
+
+// READ_SLOW (a sync step after the first): the slow weights are loaded.  A template, not a runtime select on the load: the
+// conditional 16-byte loads doubled the register count (210 VGPRs, occupancy 2 against 130 / 3 this way).
+template <bool SCALED, bool READ_SLOW>
+__device__ __forceinline__ void ranger_block(const RangerBlock& b) {
+  const bool write_slow = b.sync || b.first;
+  // sv: the slow weight on entry (READ_SLOW), written back when write_slow.  Selects, not branches: the flags are block-uniform
+  auto upd = [&](float& pv, float gv, float& mv, float& vv, float& sv) {
+    if constexpr (SCALED) gv *= b.inv_scale;
+    sv = b.first ? pv : sv;                                  // slow_buffer.copy_(p) at the tensor's first step
+    vv = vv * b.b2 + b.omb2 * gv * gv;                       // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
+    mv = mv * b.b1 + b.omb1 * gv;                            // exp_avg.mul_(beta1).add_(grad, alpha=1 - beta1)
+    pv = b.wd ? pv + b.decay * pv : pv;                      // p.add_(p, alpha=-wd * lr)
+    const float u = b.rect ? mv / (sqrtf(vv) + b.eps) : mv;  // p.addcdiv_(exp_avg, exp_avg_sq.sqrt().add_(eps), value=-s * lr)
+    pv = pv + b.step * u;                                    //   or p.add_(exp_avg, alpha=-s * lr)
+    sv = b.sync ? sv + b.alpha * (pv - sv) : sv;             // slow.add_(p - slow, alpha=alpha); p.copy_(slow)
+    pv = b.sync ? sv : pv;
+  };
+  float* const p = b.p;
+  const float* const g = b.g;
+  float* const m = b.m;
+  float* const v = b.v;
+  float* const slow = b.slow;
+  auto upd1 = [&](long long e) {
+    float pv = p[e], mv = m[e], vv = v[e], sv = 0.f;
+    if constexpr (READ_SLOW) sv = slow[e];
+    upd(pv, g[e], mv, vv, sv);
+    p[e] = pv; m[e] = mv; v[e] = vv;
+    if (write_slow) slow[e] = sv;
+  };
+  const long long e0 = b.e0, e1 = b.e1;
+  const bool vec = ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)slow) & 15) == 0) && (e0 & 3) == 0;
+  if (vec) {
+    const long long n4 = (e1 - e0) >> 2;
+    for (long long i0 = 0; i0 < n4; i0 += 4 * ADAM_NT) {
+      f32x4 p4[4], m4[4], v4[4], g4[4], s4[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const long long i = i0 + u * ADAM_NT + threadIdx.x;
+        s4[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (i < n4) {
+          const long long e = e0 + 4 * i;
+          p4[u] = *reinterpret_cast<const f32x4*>(p + e); g4[u] = *reinterpret_cast<const f32x4*>(g + e);
+          m4[u] = *reinterpret_cast<const f32x4*>(m + e); v4[u] = *reinterpret_cast<const f32x4*>(v + e);
+          if constexpr (READ_SLOW) s4[u] = *reinterpret_cast<const f32x4*>(slow + e);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const long long i = i0 + u * ADAM_NT + threadIdx.x;
+        if (i < n4) {
+          const long long e = e0 + 4 * i;
+          float pv[4] = {p4[u].x, p4[u].y, p4[u].z, p4[u].w}, mv[4] = {m4[u].x, m4[u].y, m4[u].z, m4[u].w};
+          float vv[4] = {v4[u].x, v4[u].y, v4[u].z, v4[u].w}, sv[4] = {s4[u].x, s4[u].y, s4[u].z, s4[u].w};
+          const float gv[4] = {g4[u].x, g4[u].y, g4[u].z, g4[u].w};
+#pragma unroll
+          for (int k = 0; k < 4; ++k) upd(pv[k], gv[k], mv[k], vv[k], sv[k]);
+          *reinterpret_cast<f32x4*>(p + e) = f32x4{pv[0], pv[1], pv[2], pv[3]};
+          *reinterpret_cast<f32x4*>(m + e) = f32x4{mv[0], mv[1], mv[2], mv[3]};
+          *reinterpret_cast<f32x4*>(v + e) = f32x4{vv[0], vv[1], vv[2], vv[3]};
+          if (write_slow) *reinterpret_cast<f32x4*>(slow + e) = f32x4{sv[0], sv[1], sv[2], sv[3]};
+        }
+      }
+    }
+    for (long long e = e0 + 4 * n4 + threadIdx.x; e < e1; e += ADAM_NT) upd1(e);
+  } else {
+    for (long long e = e0 + threadIdx.x; e < e1; e += ADAM_NT) upd1(e);
+  }
+}
+
+template <bool SCALED>
+__global__ __launch_bounds__(ADAM_NT) void ranger_group_kernel(const srk_ranger_args a, const float* __restrict__ state) {
+  RangerBlock b;
+  b.inv_scale = 1.f;
+  if constexpr (SCALED) {
+    if (state[2] != 0.f) return;            // a non-finite gradient somewhere: the whole step is skipped
+    b.inv_scale = 1.f / state[0];
+  }
+  const srk_adam_block blk = a.blocks[blockIdx.x];
+  const srk_adam_slot sl = a.slots[blk.slot];
+  const long long t = (long long)a.steps[sl.step_idx] + 1;
+  const double td = (double)t, b2t = pow(a.beta2, td);
+  const double n_max = 2.0 / (1.0 - a.beta2) - 1.0;
+  const double n_sma = n_max - 2.0 * td * b2t / (1.0 - b2t);
+  b.rect = n_sma > a.n_sma_threshold;
+  const double s = b.rect ? sqrt((1.0 - b2t) * (n_sma - 4.0) / (n_max - 4.0) * (n_sma - 2.0) / n_sma * n_max / (n_max - 2.0)) / (1.0 - pow(a.beta1, td))
+                          : 1.0 / (1.0 - pow(a.beta1, td));
+  b.step = (float)(-s * a.lr);
+  b.decay = (float)(-a.weight_decay * a.lr);
+  b.b1 = (float)a.beta1; b.b2 = (float)a.beta2; b.omb1 = (float)(1.0 - a.beta1); b.omb2 = (float)(1.0 - a.beta2);
+  b.eps = (float)a.eps; b.alpha = (float)a.alpha;
+  b.wd = a.weight_decay != 0.0; b.sync = t % a.k == 0; b.first = t == 1;
+  b.e0 = blk.start; b.e1 = (b.e0 + blk.count < sl.n) ? b.e0 + blk.count : sl.n;
+  b.p = sl.p; b.g = sl.g;
+  b.m = a.m + sl.state_off; b.v = a.v + sl.state_off; b.slow = a.slow + sl.state_off;
+  if (b.sync && !b.first) ranger_block<SCALED, true>(b);
+  else ranger_block<SCALED, false>(b);
+}
+
+// second launch of a Ranger step: advance the counts of the tensors in the table (adam_bump_kernel's job, on the Ranger table)
+__global__ __launch_bounds__(ADAM_NT) void ranger_bump_kernel(const srk_ranger_args a, const float* __restrict__ state) {
+  if (state && state[2] != 0.f) return;
+  for (int i = blockIdx.x * ADAM_NT + threadIdx.x; i < a.nslots; i += gridDim.x * ADAM_NT) a.steps[a.slots[i].step_idx] += 1.f;
+}
+
 }  // namespace
 
 extern "C" int srk_adam_step(const srk_adam_args* a, srk_stream_t stream) {
@@ -175,6 +297,66 @@ extern "C" int srk_adam_update_scaled(const srk_adam_args* a, const float* scale
 extern "C" int srk_loss_scale_update(float* scaler_state, srk_stream_t stream) {
   SRK_CHECK_ARG(scaler_state, "srk_loss_scale_update: null pointer");
   hipLaunchKernelGGL(scaler_update_kernel, dim3(1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), scaler_state);
+  SRK_LAUNCH_CHECK();
+  return 0;
+}
+
+
+// ---- Ranger entry points: the same four shapes as Adam's (one group; one group under loss scaling; check / update halves) ----
+namespace {
+int ranger_check_args(const srk_ranger_args* a, const char* fn) {
+  SRK_CHECK_ARG(a && a->slots && a->blocks && a->m && a->v && a->slow && a->steps, "%s: null pointer", fn);
+  SRK_CHECK_ARG(a->nblocks > 0 && a->nslots > 0, "%s: %d blocks, %d tensors", fn, a->nblocks, a->nslots);
+  SRK_CHECK_ARG(a->lr > 0.0 && a->alpha >= 0.0 && a->alpha <= 1.0 && a->k >= 1 && a->beta1 >= 0.0 && a->beta1 < 1.0 &&
+                a->beta2 >= 0.0 && a->beta2 < 1.0 && a->eps >= 0.0 && a->weight_decay >= 0.0,
+                "%s: lr=%g alpha=%g k=%d betas=(%g, %g) eps=%g weight_decay=%g", fn, a->lr, a->alpha, a->k, a->beta1, a->beta2,
+                a->eps, a->weight_decay);
+  return 0;
+}
+
+void ranger_launch(const srk_ranger_args* a, const float* scaler_state, hipStream_t st) {
+  if (scaler_state) hipLaunchKernelGGL(ranger_group_kernel<true>, dim3((unsigned)a->nblocks), dim3(ADAM_NT), 0, st, *a, scaler_state);
+  else hipLaunchKernelGGL(ranger_group_kernel<false>, dim3((unsigned)a->nblocks), dim3(ADAM_NT), 0, st, *a, scaler_state);
+  hipLaunchKernelGGL(ranger_bump_kernel, dim3((unsigned)((a->nslots + ADAM_NT - 1) / ADAM_NT)), dim3(ADAM_NT), 0, st, *a, scaler_state);
+}
+
+// the gradient check is Adam's: it reads the table only
+void ranger_check_launch(const srk_ranger_args* a, float* scaler_state, hipStream_t st) {
+  srk_adam_args c{};
+  c.slots = a->slots; c.blocks = a->blocks; c.nslots = a->nslots; c.nblocks = a->nblocks;
+  hipLaunchKernelGGL(adam_check_kernel, dim3((unsigned)a->nblocks), dim3(ADAM_NT), 0, st, c, scaler_state);
+}
+}  // namespace
+
+extern "C" int srk_ranger_step(const srk_ranger_args* a, srk_stream_t stream) {
+  if (int rc = ranger_check_args(a, "srk_ranger_step")) return rc;
+  ranger_launch(a, nullptr, reinterpret_cast<hipStream_t>(stream));
+  SRK_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int srk_ranger_step_scaled(const srk_ranger_args* a, float* scaler_state, srk_stream_t stream) {
+  if (int rc = ranger_check_args(a, "srk_ranger_step_scaled")) return rc;
+  SRK_CHECK_ARG(scaler_state, "srk_ranger_step_scaled: null scaler state");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  ranger_check_launch(a, scaler_state, st);
+  ranger_launch(a, scaler_state, st);
+  SRK_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int srk_ranger_check_scaled(const srk_ranger_args* a, float* scaler_state, srk_stream_t stream) {
+  SRK_CHECK_ARG(a && a->slots && a->blocks && scaler_state, "srk_ranger_check_scaled: null pointer");
+  SRK_CHECK_ARG(a->nblocks > 0 && a->nslots > 0, "srk_ranger_check_scaled: %d blocks, %d tensors", a->nblocks, a->nslots);
+  ranger_check_launch(a, scaler_state, reinterpret_cast<hipStream_t>(stream));
+  SRK_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int srk_ranger_update_scaled(const srk_ranger_args* a, const float* scaler_state, srk_stream_t stream) {
+  if (int rc = ranger_check_args(a, "srk_ranger_update_scaled")) return rc;
+  SRK_CHECK_ARG(scaler_state, "srk_ranger_update_scaled: null scaler state");
+  ranger_launch(a, scaler_state, reinterpret_cast<hipStream_t>(stream));
   SRK_LAUNCH_CHECK();
   return 0;
 }

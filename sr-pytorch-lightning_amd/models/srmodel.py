@@ -85,9 +85,10 @@ _supported_losses = {"l1": _l1_loss, "l2": F.mse_loss, "mae": _l1_loss, "mse": F
 _out_of_scope_losses = {"adaptive", "dists", "edge_loss", "lpips", "pencil_sketch", "pieapp"}
 
 # models/srmodel.py:57-64
-# 'ADAM' is torch.optim.Adam with the update of GPU parameters as one HIP launch (sr-pytorch-lightning_amd/optim.py)
-_supported_optimizers = {"ADAM": _hip_optim.Adam, "RMSprop": optim.RMSprop, "SGD": optim.SGD}
-_out_of_scope_optimizers = {"Ranger", "RangerVA", "RangerQH"}
+# 'ADAM' is torch.optim.Adam and 'Ranger' is torch_optimizer.Ranger, each with the update of GPU parameters as one HIP launch
+# (sr-pytorch-lightning_amd/optim.py); RangerVA and RangerQH are not built
+_supported_optimizers = {"ADAM": _hip_optim.Adam, "Ranger": _hip_optim.Ranger, "RMSprop": optim.RMSprop, "SGD": optim.SGD}
+_out_of_scope_optimizers = {"RangerVA", "RangerQH"}
 
 
 def _psnr(x, y):

@@ -6,9 +6,13 @@ update as ONE launch of `srk_adam_step` (csrc/optim.hip) instead of one launch p
 same `state_dict()` layout (`step`, `exp_avg`, `exp_avg_sq` per parameter), same arithmetic in fp32.  The step count lives
 on the device, so `step()` can be captured into a hipGraph and replayed.
 
+`Ranger` is torch_optimizer 0.3.0's `Ranger` (RAdam + Lookahead; the reference's `_supported_optimizers['Ranger']`) on the same
+table and the same kind of single launch, `srk_ranger_step`.
+
 Nothing here falls back to PyTorch arithmetic: parameters must be fp32 tensors on a GPU and the HIP library must load.
 """
 import ctypes as C
+import math
 
 import torch
 
@@ -71,12 +75,13 @@ class _Table:
 
 
 class _Plan:
-    """Per parameter group: flat moment buffers, the device step counter and the device tables of (parameter, gradient)."""
+    """Per parameter group: flat state buffers, the device step counter and the device tables of (parameter, gradient)."""
 
     def __init__(self):
-        self.offsets = {}       # param -> offset (floats) into the flat moment buffers
+        self.offsets = {}       # param -> offset (floats) into the flat state buffers
         self.index = {}         # param -> index into `steps`
-        self.m = self.v = None
+        self.flat = {}          # state key -> flat buffer of every tensor's values (exp_avg, exp_avg_sq[, slow_buffer])
+        self.m = self.v = None  # flat["exp_avg"], flat["exp_avg_sq"]
         self.steps = self.ticket = None  # per-parameter update counts (torch counts per parameter)
         self.cap = 0
         self.eager = None       # _Table of the launch-by-launch steps
@@ -84,28 +89,15 @@ class _Plan:
         self.spare = None       # allocated OUTSIDE any capture (page-locked allocations are not capturable) for the next one
 
 
-class Adam(torch.optim.Adam):
-    """torch.optim.Adam(params, lr, betas, eps, weight_decay, amsgrad) with a single-launch step for GPU parameters.
+class _TableStep:
+    """What the single-launch optimizers share: per parameter group a `_Plan` (flat state buffers, device step counts, the
+    device tables of (parameter, gradient)), the capture bookkeeping and the launches (one group; several groups under a
+    `DeviceGradScaler`: every check first).  The subclass names its flat state (`_flat_keys`), its entry points (`_entry`:
+    <entry>_step, _step_scaled, _check_scaled, _update_scaled), its launch arguments (`_args`) and its CPU form (`_cpu_step`)."""
 
-    `amsgrad=True` is not implemented (the reference never sets it); `maximize` and L2 `weight_decay` are.  A model whose
-    parameters live on the CPU (SRCNN, the reference's CPU-runnable case, runs on torch ops there) steps through
-    torch.optim.Adam itself; GPU parameters always take the HIP kernel and raise if the library is missing."""
-
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False, *, maximize=False):
-        if not 0.0 <= lr:
-            raise ValueError(f"Invalid learning rate: {lr}")
-        if not 0.0 <= eps:
-            raise ValueError(f"Invalid epsilon value: {eps}")
-        if not 0.0 <= betas[0] < 1.0:
-            raise ValueError(f"Invalid beta parameter at index 0: {betas[0]}")
-        if not 0.0 <= betas[1] < 1.0:
-            raise ValueError(f"Invalid beta parameter at index 1: {betas[1]}")
-        if not 0.0 <= weight_decay:
-            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
-        if amsgrad:
-            raise NotImplementedError("amsgrad is not implemented by the HIP Adam (the reference never enables it)")
-        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=maximize)
-        self._plans = {}
+    _flat_keys = ("exp_avg", "exp_avg_sq")
+    _entry = "srk_adam"
+    _sparse_msg = "Adam does not support sparse gradients, please consider SparseAdam instead"
 
     # -- state ------------------------------------------------------------------------------------
     def _plan(self, gi, group):
@@ -118,16 +110,16 @@ class Adam(torch.optim.Adam):
         dev = params[0].device
         for p in params:
             if not p.is_cuda:
-                raise RuntimeError("sr-pytorch-lightning_amd.optim.Adam runs on the GPU only (parameters are on %s); there is no CPU path" % p.device)
+                raise RuntimeError("sr-pytorch-lightning_amd.optim.%s runs on the GPU only (parameters are on %s); there is no CPU path" % (type(self).__name__, p.device))
             if p.dtype != torch.float32 or not p.is_contiguous() or p.device != dev:
-                raise RuntimeError("HIP Adam needs contiguous fp32 parameters on one device")
+                raise RuntimeError("HIP %s needs contiguous fp32 parameters on one device" % type(self).__name__)
         plan = _Plan()
         off = 0
         for k, p in enumerate(params):
             plan.offsets[p], plan.index[p] = off, k
             off += (p.numel() + 3) // 4 * 4                 # every tensor starts 16-byte aligned
-        plan.m = torch.zeros(max(off, 4), dtype=torch.float32, device=dev)
-        plan.v = torch.zeros(max(off, 4), dtype=torch.float32, device=dev)
+        plan.flat = {key: torch.zeros(max(off, 4), dtype=torch.float32, device=dev) for key in self._flat_keys}
+        plan.m, plan.v = plan.flat["exp_avg"], plan.flat["exp_avg_sq"]
         plan.steps = torch.zeros(len(params), dtype=torch.float32, device=dev)
         plan.ticket = torch.zeros(1, dtype=torch.int32, device=dev)
         # table of the largest case (every parameter has a gradient): tensors | 16-byte gap | blocks
@@ -138,12 +130,13 @@ class Adam(torch.optim.Adam):
         for k, p in enumerate(params):
             st = self.state[p]
             o, n = plan.offsets[p], p.numel()
-            mv, vv = plan.m[o:o + n].view_as(p), plan.v[o:o + n].view_as(p)
+            views = {key: buf[o:o + n].view_as(p) for key, buf in plan.flat.items()}
             if "exp_avg" in st:                              # loaded (load_state_dict) or carried-over (add_param_group) state
-                mv.copy_(st["exp_avg"])
-                vv.copy_(st["exp_avg_sq"])
-                host_steps[k] = float(st.get("step", 0))
-            st["exp_avg"], st["exp_avg_sq"], st["step"] = mv, vv, plan.steps[k]
+                for key, view in views.items():
+                    view.copy_(st[key])
+                host_steps[k] = float(st.get("step", 0))     # (an int or a tensor)
+            st.update(views)
+            st["step"] = plan.steps[k]
         if any(host_steps):
             plan.steps.copy_(torch.tensor(host_steps, dtype=torch.float32))
         self._plans[gi] = plan
@@ -197,9 +190,9 @@ class Adam(torch.optim.Adam):
                 return t
         for p, g in live:
             if g.is_sparse:
-                raise RuntimeError("Adam does not support sparse gradients, please consider SparseAdam instead")
+                raise RuntimeError(self._sparse_msg)
             if g.dtype != torch.float32 or not g.is_contiguous() or g.device != p.device or g.numel() != p.numel():
-                raise RuntimeError("HIP Adam needs contiguous fp32 gradients on the parameter's device")
+                raise RuntimeError("HIP %s needs contiguous fp32 gradients on the parameter's device" % type(self).__name__)
         ids = tuple(id(p) for p, _ in live)
         same_set = ids == t.live_ids                         # only addresses moved (eager steps re-allocate the gradients)
         if not same_set:
@@ -247,9 +240,9 @@ class Adam(torch.optim.Adam):
         if on_gpu == {False}:
             if grad_scaler is not None:
                 raise RuntimeError("DeviceGradScaler needs GPU parameters")
-            return super().step(closure)
+            return self._cpu_step(closure)
         if on_gpu != {True}:
-            raise RuntimeError("Adam: parameters on both CPU and GPU")
+            raise RuntimeError("%s: parameters on both CPU and GPU" % type(self).__name__)
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -263,34 +256,155 @@ class Adam(torch.optim.Adam):
                 t = self._table(plan, group)
                 if t.nblocks == 0:
                     continue
-                b1, b2 = group["betas"]
-                a = L.AdamArgs(slots=t.table.data_ptr(), blocks=t.table.data_ptr() + t.blocks_off,
-                               nslots=t.nslots, nblocks=t.nblocks,
-                               m=plan.m.data_ptr(), v=plan.v.data_ptr(), steps=plan.steps.data_ptr(), ticket=plan.ticket.data_ptr(),
-                               lr=float(group["lr"]), beta1=float(b1), beta2=float(b2), eps=float(group["eps"]),
-                               weight_decay=float(group["weight_decay"]), maximize=int(bool(group["maximize"])),
-                               one_minus_beta1=1.0 - float(b1), one_minus_beta2=1.0 - float(b2))
-                launches.append((plan, t, a))
+                launches.append((plan, t, self._args(plan, t, group)))
+        lib, e = L.load(), self._entry
         # torch.amp.GradScaler.step looks at EVERY group's gradients before it steps any: with several groups all checks come first
         # (an inf in group 1 used to leave group 0 updated); one group keeps the combined entry point (same three launches)
         split = grad_scaler is not None and len(launches) > 1
         if split:
             for plan, t, a in launches:
                 with torch.cuda.device(plan.m.device):
-                    L.check(L.load().srk_adam_check_scaled(C.byref(a), grad_scaler.state.data_ptr(), torch.cuda.current_stream().cuda_stream), "srk_adam_check_scaled")
+                    L.check(getattr(lib, e + "_check_scaled")(C.byref(a), grad_scaler.state.data_ptr(), torch.cuda.current_stream().cuda_stream), e + "_check_scaled")
         for plan, t, a in launches:
             with torch.cuda.device(plan.m.device):
                 stream = torch.cuda.current_stream().cuda_stream
                 if grad_scaler is None:
-                    L.call("srk_adam_step", a, stream)
+                    L.call(e + "_step", a, stream)
                 elif split:
-                    L.check(L.load().srk_adam_update_scaled(C.byref(a), grad_scaler.state.data_ptr(), stream), "srk_adam_update_scaled")
+                    L.check(getattr(lib, e + "_update_scaled")(C.byref(a), grad_scaler.state.data_ptr(), stream), e + "_update_scaled")
                 else:
-                    L.check(L.load().srk_adam_step_scaled(C.byref(a), grad_scaler.state.data_ptr(), stream), "srk_adam_step_scaled")
+                    L.check(getattr(lib, e + "_step_scaled")(C.byref(a), grad_scaler.state.data_ptr(), stream), e + "_step_scaled")
                 # the kernel wrote through raw pointers: tell autograd (and the packed-weight cache, which keys on it) that
                 # the parameters changed, as an in-place torch op would
                 torch.autograd.graph.increment_version(t.live)
         if grad_scaler is not None:
             with torch.cuda.device(grad_scaler.state.device):
-                L.check(L.load().srk_loss_scale_update(grad_scaler.state.data_ptr(), torch.cuda.current_stream().cuda_stream), "srk_loss_scale_update")
+                L.check(lib.srk_loss_scale_update(grad_scaler.state.data_ptr(), torch.cuda.current_stream().cuda_stream), "srk_loss_scale_update")
+        return loss
+
+
+class Adam(_TableStep, torch.optim.Adam):
+    """torch.optim.Adam(params, lr, betas, eps, weight_decay, amsgrad) with a single-launch step for GPU parameters.
+
+    `amsgrad=True` is not implemented (the reference never sets it); `maximize` and L2 `weight_decay` are.  A model whose
+    parameters live on the CPU (SRCNN, the reference's CPU-runnable case, runs on torch ops there) steps through
+    torch.optim.Adam itself; GPU parameters always take the HIP kernel and raise if the library is missing."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False, *, maximize=False):
+        if not 0.0 <= lr:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 <= eps:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        if not 0.0 <= betas[0] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 0: {betas[0]}")
+        if not 0.0 <= betas[1] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 1: {betas[1]}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        if amsgrad:
+            raise NotImplementedError("amsgrad is not implemented by the HIP Adam (the reference never enables it)")
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=maximize)
+        self._plans = {}
+
+    def _args(self, plan, t, group):
+        b1, b2 = group["betas"]
+        return L.AdamArgs(slots=t.table.data_ptr(), blocks=t.table.data_ptr() + t.blocks_off,
+                          nslots=t.nslots, nblocks=t.nblocks,
+                          m=plan.m.data_ptr(), v=plan.v.data_ptr(), steps=plan.steps.data_ptr(), ticket=plan.ticket.data_ptr(),
+                          lr=float(group["lr"]), beta1=float(b1), beta2=float(b2), eps=float(group["eps"]),
+                          weight_decay=float(group["weight_decay"]), maximize=int(bool(group["maximize"])),
+                          one_minus_beta1=1.0 - float(b1), one_minus_beta2=1.0 - float(b2))
+
+    def _cpu_step(self, closure):
+        return torch.optim.Adam.step(self, closure)
+
+
+
+
+def ranger_scalars(t, beta1, beta2, n_sma_threshhold):
+    """(rectified, step size) of a tensor's t-th Ranger step, in double: torch_optimizer's RAdam scalars (srk.h has the rule)."""
+    b2t = beta2 ** t
+    n_max = 2 / (1 - beta2) - 1
+    n_sma = n_max - 2 * t * b2t / (1 - b2t)
+    if n_sma > n_sma_threshhold:
+        return True, math.sqrt((1 - b2t) * (n_sma - 4) / (n_max - 4) * (n_sma - 2) / n_sma * n_max / (n_max - 2)) / (1 - beta1 ** t)
+    return False, 1.0 / (1 - beta1 ** t)
+
+
+class Ranger(_TableStep, torch.optim.Optimizer):
+    """torch_optimizer.Ranger (0.3.0: RAdam + Lookahead) with a single-launch step for GPU parameters.
+
+    Same constructor, same group keys (`N_sma_threshhold` spelled as there), same per-parameter state (`step`, `exp_avg`,
+    `exp_avg_sq`, `slow_buffer`).  One deliberate difference: the package caches RAdam's (N_sma, step size) per step count in a
+    buffer shared by ALL groups, so a second group with other betas reuses the first group's scalars; here every tensor's
+    scalars come from its own group (the same numbers whenever the groups share betas).  A model whose parameters live on the
+    CPU steps through a plain-torch fp32 form of the same rule; GPU parameters always take `srk_ranger_step`."""
+
+    _flat_keys = ("exp_avg", "exp_avg_sq", "slow_buffer")
+    _entry = "srk_ranger"
+    _sparse_msg = "Ranger optimizer does not support sparse gradients"
+
+    def __init__(self, params, lr=1e-3, alpha=0.5, k=6, N_sma_threshhold=5, betas=(0.95, 0.999), eps=1e-5, weight_decay=0):
+        if not lr > 0:
+            raise ValueError(f"Invalid Learning Rate: {lr}")
+        if not 0.0 <= alpha <= 1.0:
+            raise ValueError(f"Invalid slow update rate: {alpha}")
+        if not 1 <= k:
+            raise ValueError(f"Invalid lookahead steps: {k}")
+        if not 0.0 <= betas[0] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 0: {betas[0]}")
+        if not 0.0 <= betas[1] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 1: {betas[1]}")
+        if not 0.0 <= eps:
+            raise ValueError(f"Invalid eps: {eps}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        defaults = dict(lr=lr, alpha=alpha, k=k, step_counter=0, betas=betas, N_sma_threshhold=N_sma_threshhold, eps=eps,
+                        weight_decay=weight_decay)
+        super().__init__(params, defaults)
+        self._plans = {}
+
+    def _args(self, plan, t, group):
+        b1, b2 = group["betas"]
+        return L.RangerArgs(slots=t.table.data_ptr(), blocks=t.table.data_ptr() + t.blocks_off, nslots=t.nslots, nblocks=t.nblocks,
+                            m=plan.m.data_ptr(), v=plan.v.data_ptr(), slow=plan.flat["slow_buffer"].data_ptr(),
+                            steps=plan.steps.data_ptr(), lr=float(group["lr"]), beta1=float(b1), beta2=float(b2),
+                            alpha=float(group["alpha"]), n_sma_threshold=float(group["N_sma_threshhold"]), eps=float(group["eps"]),
+                            weight_decay=float(group["weight_decay"]), k=int(group["k"]))
+
+    def _cpu_step(self, closure):
+        """The package's step in torch fp32 ops (CPU parameters), with the scalars of each tensor's own group."""
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        for group in self.param_groups:
+            b1, b2 = group["betas"]
+            lr, wd, thr = group["lr"], group["weight_decay"], group["N_sma_threshhold"]
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                g = p.grad
+                if g.is_sparse:
+                    raise RuntimeError(self._sparse_msg)
+                st = self.state[p]
+                if len(st) == 0:
+                    st["step"] = 0
+                    st["exp_avg"], st["exp_avg_sq"] = torch.zeros_like(p), torch.zeros_like(p)
+                    st["slow_buffer"] = p.detach().clone()
+                m, v = st["exp_avg"], st["exp_avg_sq"]
+                v.mul_(b2).addcmul_(g, g, value=1 - b2)
+                m.mul_(b1).add_(g, alpha=1 - b1)
+                t = st["step"] = int(st["step"]) + 1
+                rect, s = ranger_scalars(t, b1, b2, thr)
+                if wd != 0:
+                    p.add_(p, alpha=-wd * lr)
+                if rect:
+                    p.addcdiv_(m, v.sqrt().add_(group["eps"]), value=-s * lr)
+                else:
+                    p.add_(m, alpha=-s * lr)
+                if t % group["k"] == 0:
+                    slow = st["slow_buffer"]
+                    slow.add_(p - slow, alpha=group["alpha"])
+                    p.copy_(slow)
         return loss
