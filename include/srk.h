@@ -835,6 +835,54 @@ int srk_ranger_step_scaled(const srk_ranger_args* a, float* scaler_state, srk_st
 int srk_ranger_check_scaled(const srk_ranger_args* a, float* scaler_state, srk_stream_t stream);
 int srk_ranger_update_scaled(const srk_ranger_args* a, const float* scaler_state, srk_stream_t stream);
 
+/* ---- optimizer: SGD (torch.optim.SGD) over the same table -------------------------------------------------------------------
+ * The models' `optimizer="SGD"` (reference models/srmodel.py:57-64).  The tensors and blocks are srk_adam_slot / srk_adam_block;
+ * `buf` is the flat momentum_buffer of all tensors (tensor i at `state_off`; NULL iff momentum == 0).  Per tensor:
+ *     g' = maximize ? -g : g;   g' += weight_decay * p                        (weight_decay != 0)
+ *     momentum != 0:  buf = steps[step_idx] == 0 ? g' : momentum * buf + (1 - dampening) * g'
+ *                     g' = nesterov ? g' + momentum * buf : buf
+ *     p += (-lr) * g'
+ * "first" (steps[step_idx] == 0) is torch's `momentum_buffer is None`: the buffer starts as a copy of the first gradient the
+ * tensor ever receives, whatever `dampening` is.  It is read from the DEVICE count, which the call itself advances (a second
+ * tiny launch) for the tensors in the table: a tensor without a gradient is not in the table and stays "first", and a replayed
+ * hipGraph takes the branch of the step it replays.  momentum == 0: neither `buf` nor `steps` is read or written (both may be NULL).
+ * -lr and 1 - dampening are formed in double and rounded to fp32 once; the element arithmetic is fp32 in torch's order.
+ * Traffic: 12 B per parameter (p read + written, g read); 20 B with momentum (16 B at a tensor's first step: buf is only written).
+ * srk_sgd_step_scaled / _check_scaled / _update_scaled: srk_adam_*'s loss-scaling contract (a step with a non-finite gradient changes
+ * nothing, the counts and so the "first" flags included; then srk_loss_scale_update). */
+typedef struct {
+  const srk_adam_slot* slots; const srk_adam_block* blocks; int nslots, nblocks;
+  float* buf;
+  float* steps;
+  double lr, momentum, dampening, weight_decay;
+  int nesterov, maximize;
+} srk_sgd_args;
+int srk_sgd_step(const srk_sgd_args* a, srk_stream_t stream);
+int srk_sgd_step_scaled(const srk_sgd_args* a, float* scaler_state, srk_stream_t stream);
+int srk_sgd_check_scaled(const srk_sgd_args* a, float* scaler_state, srk_stream_t stream);
+int srk_sgd_update_scaled(const srk_sgd_args* a, const float* scaler_state, srk_stream_t stream);
+
+/* ---- optimizer: RMSprop (torch.optim.RMSprop) over the same table -----------------------------------------------------------
+ * The models' `optimizer="RMSprop"`.  `sq`, `buf`, `ga` are the flat square_avg, momentum_buffer (NULL iff momentum == 0) and
+ * grad_avg (NULL iff !centered) of all tensors.  Per tensor, with g' as for SGD:
+ *     sq = alpha * sq + (1 - alpha) * g' * g'
+ *     centered:  ga += (g' - ga) * (1 - alpha);  avg = sqrt(sq - ga * ga) + eps          else  avg = sqrt(sq) + eps
+ *     momentum > 0:  buf = momentum * buf + g' / avg;  p += (-lr) * buf                  else  p += (-lr) * (g' / avg)
+ * Only the buffers the configuration uses are touched: 20 B per parameter plain, +8 B with momentum, +8 B centered.  Scalars as
+ * for SGD; `steps` (torch's per-parameter `step`) advance as srk_adam_step's do.  _step_scaled / _check_scaled / _update_scaled:
+ * srk_adam_*'s loss-scaling contract (then srk_loss_scale_update). */
+typedef struct {
+  const srk_adam_slot* slots; const srk_adam_block* blocks; int nslots, nblocks;
+  float* sq; float* buf; float* ga;
+  float* steps;
+  double lr, alpha, eps, weight_decay, momentum;
+  int centered, maximize;
+} srk_rmsprop_args;
+int srk_rmsprop_step(const srk_rmsprop_args* a, srk_stream_t stream);
+int srk_rmsprop_step_scaled(const srk_rmsprop_args* a, float* scaler_state, srk_stream_t stream);
+int srk_rmsprop_check_scaled(const srk_rmsprop_args* a, float* scaler_state, srk_stream_t stream);
+int srk_rmsprop_update_scaled(const srk_rmsprop_args* a, const float* scaler_state, srk_stream_t stream);
+
 /* ---- misc ------------------------------------------------------------------------------------------ */
 const char* srk_last_error(void);
 int srk_version(void);

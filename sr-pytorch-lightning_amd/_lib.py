@@ -113,6 +113,18 @@ class RangerArgs(C.Structure):
                 ("n_sma_threshold", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double), ("k", _i)]
 
 
+class SgdArgs(C.Structure):
+    _fields_ = [("slots", _p), ("blocks", _p), ("nslots", _i), ("nblocks", _i), ("buf", _p), ("steps", _p),
+                ("lr", C.c_double), ("momentum", C.c_double), ("dampening", C.c_double), ("weight_decay", C.c_double),
+                ("nesterov", _i), ("maximize", _i)]
+
+
+class RmspropArgs(C.Structure):
+    _fields_ = [("slots", _p), ("blocks", _p), ("nslots", _i), ("nblocks", _i), ("sq", _p), ("buf", _p), ("ga", _p), ("steps", _p),
+                ("lr", C.c_double), ("alpha", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double), ("momentum", C.c_double),
+                ("centered", _i), ("maximize", _i)]
+
+
 class WgradArgs(C.Structure):
     _fields_ = [("x", _p), ("x_pitch", _i), ("x_coff", _i), ("x_ps", _i),
                 ("dy", _p), ("dy_pitch", _i), ("dy_coff", _i), ("dy_ps", _i),
@@ -256,6 +268,8 @@ LAUNCHERS = {
     "srk_pw_wgrad": PwWgradArgs,
     "srk_adam_step": AdamArgs,
     "srk_ranger_step": RangerArgs,
+    "srk_sgd_step": SgdArgs,
+    "srk_rmsprop_step": RmspropArgs,
     "srk_chan_finalize": ChanFinalizeArgs,
     "srk_conv2d_wgrad": WgradArgs,
     "srk_wgrad_finalize": WgradFinArgs,
@@ -296,6 +310,8 @@ OTHER_SYMBOLS = ("srk_conv_tile", "srk_last_error", "srk_version", "srk_device_c
                  "srk_proj_pack", "srk_proj_pack_bytes", "srk_proj_wgrad_scratch_floats", "srk_proj_pack_group", "srk_wgrad_slab_cout",
                  "srk_hrtail_scratch_floats", "srk_adam_step_scaled", "srk_adam_check_scaled", "srk_adam_update_scaled", "srk_loss_scale_update", "srk_conv_bits_ok",
                  "srk_ranger_step_scaled", "srk_ranger_check_scaled", "srk_ranger_update_scaled",
+                 "srk_sgd_step_scaled", "srk_sgd_check_scaled", "srk_sgd_update_scaled",
+                 "srk_rmsprop_step_scaled", "srk_rmsprop_check_scaled", "srk_rmsprop_update_scaled",
                  "srk_conv_trunk", "srk_conv_trunk_ok", "srk_flip_blocks", "srk_flip_mean",
                  "srk_ms_ssim_workspace_bytes", "srk_ms_ssim_tiles", "srk_haarpsi_tiles")
 
@@ -424,6 +440,11 @@ def load():
         for fn in (lib.srk_ranger_step_scaled, lib.srk_ranger_check_scaled, lib.srk_ranger_update_scaled):
             fn.argtypes = [C.POINTER(RangerArgs), C.c_void_p, C.c_void_p]
             fn.restype = C.c_int
+    for entry, st in (("srk_sgd", SgdArgs), ("srk_rmsprop", RmspropArgs)):
+        if not isinstance(getattr(lib, entry + "_step_scaled", None), _Absent):
+            for fn in (getattr(lib, entry + sfx) for sfx in ("_step_scaled", "_check_scaled", "_update_scaled")):
+                fn.argtypes = [C.POINTER(st), C.c_void_p, C.c_void_p]
+                fn.restype = C.c_int
     lib.srk_loss_scale_update.argtypes = [C.c_void_p, C.c_void_p]
     lib.srk_loss_scale_update.restype = C.c_int
     lib.srk_last_error.restype = C.c_char_p

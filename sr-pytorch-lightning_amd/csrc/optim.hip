@@ -360,3 +360,265 @@ extern "C" int srk_ranger_update_scaled(const srk_ranger_args* a, const float* s
   SRK_LAUNCH_CHECK();
   return 0;
 }
+
+
+// ---- SGD and RMSprop (torch.optim.SGD / torch.optim.RMSprop) over the same table ---------------------------------------------
+// The models' `optimizer="SGD"` / `"RMSprop"` (reference models/srmodel.py:57-64).  torch's foreach step packs a few dozen tensors
+// per launch and makes one pass per _foreach_* op: for RCAN's ~1,600 tensors that is Adam's launch storm once per pass.  Here:
+// one launch over Adam's table, one tensor per block, so every per-tensor decision is block-uniform.  srk.h has the rules; the
+// element arithmetic is fp32 in the order of torch's _single_tensor_sgd / _single_tensor_rmsprop, and every scalar (-lr,
+// 1 - dampening, 1 - alpha) is formed in double and rounded to fp32 once, as torch rounds a Python scalar.
+// Only the state a configuration uses is touched: SGD 12 B per parameter (p read + written, g read), 20 B with momentum;
+// RMSprop 20 B (square_avg too), +8 B with momentum, +8 B centered.
+namespace {
+
+// The elements [e0, e1) of one tensor with NS flat state arrays beside p and g: 16-byte accesses when every address allows it,
+// 4 x float4 per array and thread with all loads issued before the first use (a 4096-element block is one pass), scalar tail.
+// upd(p, g, s[NS]) is the element rule.  READ0 = false: state array 0 is written without being read (SGD's momentum buffer at a
+// tensor's first step) -- a template, not a runtime select on the load, for the reason given at ranger_block.
+template <int NS, bool READ0, class F>
+__device__ __forceinline__ void state_block(float* const p, const float* const g, float* const (&s)[NS > 0 ? NS : 1],
+                                            const long long e0, const long long e1, F upd) {
+  constexpr int NA = NS > 0 ? NS : 1;
+  auto upd1 = [&](long long e) {
+    float pv = p[e], sv[NA] = {};
+#pragma unroll
+    for (int j = 0; j < NS; ++j)
+      if (READ0 || j > 0) sv[j] = s[j][e];
+    upd(pv, g[e], sv);
+    p[e] = pv;
+#pragma unroll
+    for (int j = 0; j < NS; ++j) s[j][e] = sv[j];
+  };
+  uintptr_t bits = (uintptr_t)p | (uintptr_t)g;
+#pragma unroll
+  for (int j = 0; j < NS; ++j) bits |= (uintptr_t)s[j];
+  const bool vec = (bits & 15) == 0 && (e0 & 3) == 0;
+  if (vec) {
+    const long long n4 = (e1 - e0) >> 2;
+    for (long long i0 = 0; i0 < n4; i0 += 4 * ADAM_NT) {
+      f32x4 p4[4], g4[4], s4[NA][4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const long long i = i0 + u * ADAM_NT + threadIdx.x;
+#pragma unroll
+        for (int j = 0; j < NA; ++j) s4[j][u] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (i < n4) {
+          const long long e = e0 + 4 * i;
+          p4[u] = *reinterpret_cast<const f32x4*>(p + e); g4[u] = *reinterpret_cast<const f32x4*>(g + e);
+#pragma unroll
+          for (int j = 0; j < NS; ++j)
+            if (READ0 || j > 0) s4[j][u] = *reinterpret_cast<const f32x4*>(s[j] + e);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const long long i = i0 + u * ADAM_NT + threadIdx.x;
+        if (i < n4) {
+          const long long e = e0 + 4 * i;
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            float pv = p4[u][k], sv[NA] = {};
+#pragma unroll
+            for (int j = 0; j < NS; ++j) sv[j] = s4[j][u][k];
+            upd(pv, g4[u][k], sv);
+            p4[u][k] = pv;
+#pragma unroll
+            for (int j = 0; j < NS; ++j) s4[j][u][k] = sv[j];
+          }
+          *reinterpret_cast<f32x4*>(p + e) = p4[u];
+#pragma unroll
+          for (int j = 0; j < NS; ++j) *reinterpret_cast<f32x4*>(s[j] + e) = s4[j][u];
+        }
+      }
+    }
+    for (long long e = e0 + 4 * n4 + threadIdx.x; e < e1; e += ADAM_NT) upd1(e);
+  } else {
+    for (long long e = e0 + threadIdx.x; e < e1; e += ADAM_NT) upd1(e);
+  }
+}
+
+// torch.optim.SGD.  "first" -- torch creates momentum_buffer as a clone of the first gradient a tensor ever receives, whatever
+// `dampening` says -- is read from the tensor's DEVICE count, so a replayed hipGraph gives a tensor whose first gradient arrives
+// at a later step the right branch, and a step skipped under loss scaling leaves the tensor "first".
+template <bool SCALED, bool MOM>
+__global__ __launch_bounds__(ADAM_NT) void sgd_group_kernel(const srk_sgd_args a, const float* __restrict__ state) {
+  float inv_scale = 1.f;
+  if constexpr (SCALED) {
+    if (state[2] != 0.f) return;            // a non-finite gradient somewhere: the whole step is skipped
+    inv_scale = 1.f / state[0];
+  }
+  const srk_adam_block blk = a.blocks[blockIdx.x];
+  const srk_adam_slot sl = a.slots[blk.slot];
+  const float mom = (float)a.momentum, omd = (float)(1.0 - a.dampening), wd = (float)a.weight_decay, nlr = (float)(-a.lr);
+  const bool has_wd = a.weight_decay != 0.0, nesterov = a.nesterov != 0, maximize = a.maximize != 0;
+  bool first = false;
+  if constexpr (MOM) first = a.steps[sl.step_idx] == 0.f;
+  const long long e0 = blk.start, e1 = (e0 + blk.count < sl.n) ? e0 + blk.count : sl.n;
+  auto upd = [&](float& pv, float gv, float (&sv)[1]) {
+    if constexpr (SCALED) gv *= inv_scale;
+    gv = maximize ? -gv : gv;
+    gv = has_wd ? gv + wd * pv : gv;                          // grad.add(param, alpha=weight_decay)
+    if constexpr (MOM) {
+      const float b = first ? gv : sv[0] * mom + omd * gv;    // buf = grad.clone()  or  buf.mul_(momentum).add_(grad, alpha=1 - dampening)
+      sv[0] = b;
+      gv = nesterov ? gv + mom * b : b;                       // grad.add(buf, alpha=momentum)  or  buf
+    }
+    pv = pv + nlr * gv;                                       // param.add_(grad, alpha=-lr)
+  };
+  if constexpr (MOM) {
+    float* const s[1] = {a.buf + sl.state_off};
+    if (first) state_block<1, false>(sl.p, sl.g, s, e0, e1, upd);
+    else state_block<1, true>(sl.p, sl.g, s, e0, e1, upd);
+  } else {
+    float* const s[1] = {nullptr};
+    state_block<0, false>(sl.p, sl.g, s, e0, e1, upd);
+  }
+}
+
+// torch.optim.RMSprop.  State arrays in the order square_avg, [momentum_buffer], [grad_avg].
+template <bool SCALED, bool MOM, bool CENTERED>
+__global__ __launch_bounds__(ADAM_NT) void rmsprop_group_kernel(const srk_rmsprop_args a, const float* __restrict__ state) {
+  float inv_scale = 1.f;
+  if constexpr (SCALED) {
+    if (state[2] != 0.f) return;            // a non-finite gradient somewhere: the whole step is skipped
+    inv_scale = 1.f / state[0];
+  }
+  constexpr int NS = 1 + (MOM ? 1 : 0) + (CENTERED ? 1 : 0);
+  const srk_adam_block blk = a.blocks[blockIdx.x];
+  const srk_adam_slot sl = a.slots[blk.slot];
+  const float alpha = (float)a.alpha, oma = (float)(1.0 - a.alpha), eps = (float)a.eps, mom = (float)a.momentum;
+  const float wd = (float)a.weight_decay, nlr = (float)(-a.lr);
+  const bool has_wd = a.weight_decay != 0.0, maximize = a.maximize != 0;
+  const bool lerp_low = oma < 0.5f;          // at::lerp's two forms
+  const float omw = 1.f - oma;
+  const long long e0 = blk.start, e1 = (e0 + blk.count < sl.n) ? e0 + blk.count : sl.n;
+  auto upd = [&](float& pv, float gv, float (&sv)[NS]) {
+    if constexpr (SCALED) gv *= inv_scale;
+    gv = maximize ? -gv : gv;
+    gv = has_wd ? gv + wd * pv : gv;                          // grad.add(param, alpha=weight_decay)
+    float& sq = sv[0];
+    sq = sq * alpha + oma * gv * gv;                          // square_avg.mul_(alpha).addcmul_(grad, grad, value=1 - alpha)
+    float avg;
+    if constexpr (CENTERED) {
+      float& ga = sv[NS - 1];
+      const float d = gv - ga;
+      ga = lerp_low ? ga + oma * d : gv - d * omw;            // grad_avg.lerp_(grad, 1 - alpha)
+      avg = sqrtf(sq - ga * ga);                              // square_avg.addcmul(grad_avg, grad_avg, value=-1).sqrt_()
+    } else {
+      avg = sqrtf(sq);
+    }
+    avg += eps;
+    if constexpr (MOM) {
+      float& b = sv[1];
+      b = b * mom + gv / avg;                                 // buf.mul_(momentum).addcdiv_(grad, avg)
+      pv = pv + nlr * b;                                      // param.add_(buf, alpha=-lr)
+    } else {
+      pv = pv + nlr * (gv / avg);                             // param.addcdiv_(grad, avg, value=-lr)
+    }
+  };
+  float* s[NS];
+  s[0] = a.sq + sl.state_off;
+  if constexpr (MOM) s[1] = a.buf + sl.state_off;
+  if constexpr (CENTERED) s[NS - 1] = a.ga + sl.state_off;
+  float* const (&sc)[NS] = s;
+  state_block<NS, true>(sl.p, sl.g, sc, e0, e1, upd);
+}
+
+// the gradient check and the count bump are Adam's kernels: they read the table (and `steps`) only
+void table_check_launch(const srk_adam_slot* slots, const srk_adam_block* blocks, int nslots, int nblocks, float* scaler_state, hipStream_t st) {
+  srk_adam_args c{};
+  c.slots = slots; c.blocks = blocks; c.nslots = nslots; c.nblocks = nblocks;
+  hipLaunchKernelGGL(adam_check_kernel, dim3((unsigned)nblocks), dim3(ADAM_NT), 0, st, c, scaler_state);
+}
+
+void table_bump_launch(const srk_adam_slot* slots, int nslots, float* steps, const float* scaler_state, hipStream_t st) {
+  srk_adam_args c{};
+  c.slots = slots; c.nslots = nslots; c.steps = steps;
+  hipLaunchKernelGGL(adam_bump_kernel, dim3((unsigned)((nslots + ADAM_NT - 1) / ADAM_NT)), dim3(ADAM_NT), 0, st, c, scaler_state);
+}
+
+int sgd_check_args(const srk_sgd_args* a, const char* fn) {
+  SRK_CHECK_ARG(a && a->slots && a->blocks, "%s: null table", fn);
+  SRK_CHECK_ARG(a->nblocks > 0 && a->nslots > 0, "%s: %d blocks, %d tensors", fn, a->nblocks, a->nslots);
+  SRK_CHECK_ARG(a->momentum == 0.0 || (a->buf && a->steps), "%s: momentum=%g needs the momentum buffer and the counts", fn, a->momentum);
+  SRK_CHECK_ARG(a->lr >= 0.0 && a->momentum >= 0.0 && a->weight_decay >= 0.0 && (!a->nesterov || (a->momentum > 0.0 && a->dampening == 0.0)),
+                "%s: lr=%g momentum=%g dampening=%g weight_decay=%g nesterov=%d", fn, a->lr, a->momentum, a->dampening, a->weight_decay, a->nesterov);
+  return 0;
+}
+
+// momentum == 0: no count is kept (nothing is "first"), so the update is the only launch
+void sgd_launch(const srk_sgd_args* a, const float* scaler_state, hipStream_t st) {
+  const dim3 grid((unsigned)a->nblocks), block(ADAM_NT);
+  const bool mom = a->momentum != 0.0;
+  if (scaler_state) {
+    if (mom) hipLaunchKernelGGL((sgd_group_kernel<true, true>), grid, block, 0, st, *a, scaler_state);
+    else hipLaunchKernelGGL((sgd_group_kernel<true, false>), grid, block, 0, st, *a, scaler_state);
+  } else {
+    if (mom) hipLaunchKernelGGL((sgd_group_kernel<false, true>), grid, block, 0, st, *a, scaler_state);
+    else hipLaunchKernelGGL((sgd_group_kernel<false, false>), grid, block, 0, st, *a, scaler_state);
+  }
+  if (mom) table_bump_launch(a->slots, a->nslots, a->steps, scaler_state, st);
+}
+
+int rmsprop_check_args(const srk_rmsprop_args* a, const char* fn) {
+  SRK_CHECK_ARG(a && a->slots && a->blocks, "%s: null table", fn);
+  SRK_CHECK_ARG(a->nblocks > 0 && a->nslots > 0, "%s: %d blocks, %d tensors", fn, a->nblocks, a->nslots);
+  SRK_CHECK_ARG(a->sq && a->steps && (a->momentum <= 0.0 || a->buf) && (!a->centered || a->ga), "%s: null state pointer", fn);
+  SRK_CHECK_ARG(a->lr >= 0.0 && a->alpha >= 0.0 && a->eps >= 0.0 && a->momentum >= 0.0 && a->weight_decay >= 0.0,
+                "%s: lr=%g alpha=%g eps=%g momentum=%g weight_decay=%g", fn, a->lr, a->alpha, a->eps, a->momentum, a->weight_decay);
+  return 0;
+}
+
+template <bool SCALED>
+void rmsprop_launch_as(const srk_rmsprop_args* a, const float* scaler_state, hipStream_t st) {
+  const dim3 grid((unsigned)a->nblocks), block(ADAM_NT);
+  const bool mom = a->momentum > 0.0, cen = a->centered != 0;
+  if (mom && cen) hipLaunchKernelGGL((rmsprop_group_kernel<SCALED, true, true>), grid, block, 0, st, *a, scaler_state);
+  else if (mom) hipLaunchKernelGGL((rmsprop_group_kernel<SCALED, true, false>), grid, block, 0, st, *a, scaler_state);
+  else if (cen) hipLaunchKernelGGL((rmsprop_group_kernel<SCALED, false, true>), grid, block, 0, st, *a, scaler_state);
+  else hipLaunchKernelGGL((rmsprop_group_kernel<SCALED, false, false>), grid, block, 0, st, *a, scaler_state);
+}
+
+void rmsprop_launch(const srk_rmsprop_args* a, const float* scaler_state, hipStream_t st) {
+  if (scaler_state) rmsprop_launch_as<true>(a, scaler_state, st);
+  else rmsprop_launch_as<false>(a, scaler_state, st);
+  table_bump_launch(a->slots, a->nslots, a->steps, scaler_state, st);
+}
+}  // namespace
+
+// The four shapes of Adam's entry points (one group; one group under loss scaling; the check / update halves for several groups)
+#define SRK_TABLE_STEP_ENTRIES(NAME, ARGS)                                                                              \
+  extern "C" int srk_##NAME##_step(const ARGS* a, srk_stream_t stream) {                                               \
+    if (int rc = NAME##_check_args(a, "srk_" #NAME "_step")) return rc;                                                \
+    NAME##_launch(a, nullptr, reinterpret_cast<hipStream_t>(stream));                                                  \
+    SRK_LAUNCH_CHECK();                                                                                                \
+    return 0;                                                                                                          \
+  }                                                                                                                    \
+  extern "C" int srk_##NAME##_step_scaled(const ARGS* a, float* scaler_state, srk_stream_t stream) {                   \
+    if (int rc = NAME##_check_args(a, "srk_" #NAME "_step_scaled")) return rc;                                         \
+    SRK_CHECK_ARG(scaler_state, "srk_" #NAME "_step_scaled: null scaler state");                                       \
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);                                                            \
+    table_check_launch(a->slots, a->blocks, a->nslots, a->nblocks, scaler_state, st);                                  \
+    NAME##_launch(a, scaler_state, st);                                                                                \
+    SRK_LAUNCH_CHECK();                                                                                                \
+    return 0;                                                                                                          \
+  }                                                                                                                    \
+  extern "C" int srk_##NAME##_check_scaled(const ARGS* a, float* scaler_state, srk_stream_t stream) {                  \
+    SRK_CHECK_ARG(a && a->slots && a->blocks && scaler_state, "srk_" #NAME "_check_scaled: null pointer");             \
+    SRK_CHECK_ARG(a->nblocks > 0 && a->nslots > 0, "srk_" #NAME "_check_scaled: %d blocks, %d tensors", a->nblocks, a->nslots); \
+    table_check_launch(a->slots, a->blocks, a->nslots, a->nblocks, scaler_state, reinterpret_cast<hipStream_t>(stream)); \
+    SRK_LAUNCH_CHECK();                                                                                                \
+    return 0;                                                                                                          \
+  }                                                                                                                    \
+  extern "C" int srk_##NAME##_update_scaled(const ARGS* a, const float* scaler_state, srk_stream_t stream) {           \
+    if (int rc = NAME##_check_args(a, "srk_" #NAME "_update_scaled")) return rc;                                       \
+    SRK_CHECK_ARG(scaler_state, "srk_" #NAME "_update_scaled: null scaler state");                                     \
+    NAME##_launch(a, scaler_state, reinterpret_cast<hipStream_t>(stream));                                             \
+    SRK_LAUNCH_CHECK();                                                                                                \
+    return 0;                                                                                                          \
+  }
+
+SRK_TABLE_STEP_ENTRIES(sgd, srk_sgd_args)
+SRK_TABLE_STEP_ENTRIES(rmsprop, srk_rmsprop_args)
+#undef SRK_TABLE_STEP_ENTRIES

@@ -18,7 +18,6 @@ from typing import Any, Callable
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
-import torch.optim as optim
 
 from .. import optim as _hip_optim
 
@@ -85,9 +84,10 @@ _supported_losses = {"l1": _l1_loss, "l2": F.mse_loss, "mae": _l1_loss, "mse": F
 _out_of_scope_losses = {"adaptive", "dists", "edge_loss", "lpips", "pencil_sketch", "pieapp"}
 
 # models/srmodel.py:57-64
-# 'ADAM' is torch.optim.Adam and 'Ranger' is torch_optimizer.Ranger, each with the update of GPU parameters as one HIP launch
-# (sr-pytorch-lightning_amd/optim.py); RangerVA and RangerQH are not built
-_supported_optimizers = {"ADAM": _hip_optim.Adam, "Ranger": _hip_optim.Ranger, "RMSprop": optim.RMSprop, "SGD": optim.SGD}
+# 'ADAM', 'RMSprop' and 'SGD' are torch.optim.Adam / RMSprop / SGD and 'Ranger' is torch_optimizer.Ranger, each with the update of
+# GPU parameters as one HIP launch (sr-pytorch-lightning_amd/optim.py; CPU parameters step through the torch classes
+# themselves); RangerVA and RangerQH are not built
+_supported_optimizers = {"ADAM": _hip_optim.Adam, "Ranger": _hip_optim.Ranger, "RMSprop": _hip_optim.RMSprop, "SGD": _hip_optim.SGD}
 _out_of_scope_optimizers = {"RangerVA", "RangerQH"}
 
 

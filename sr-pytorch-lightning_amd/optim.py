@@ -9,6 +9,9 @@ on the device, so `step()` can be captured into a hipGraph and replayed.
 `Ranger` is torch_optimizer 0.3.0's `Ranger` (RAdam + Lookahead; the reference's `_supported_optimizers['Ranger']`) on the same
 table and the same kind of single launch, `srk_ranger_step`.
 
+`SGD` and `RMSprop` are torch.optim.SGD / torch.optim.RMSprop (`_supported_optimizers['SGD']` / `['RMSprop']`) on the same table:
+`srk_sgd_step`, `srk_rmsprop_step`.  Same constructors, `state_dict()` interchangeable with torch's in both directions.
+
 Nothing here falls back to PyTorch arithmetic: parameters must be fp32 tensors on a GPU and the HIP library must load.
 """
 import ctypes as C
@@ -80,8 +83,10 @@ class _Plan:
     def __init__(self):
         self.offsets = {}       # param -> offset (floats) into the flat state buffers
         self.index = {}         # param -> index into `steps`
+        self.keys = ()          # the state keys the group's configuration uses (`_TableStep._keys`)
         self.flat = {}          # state key -> flat buffer of every tensor's values (exp_avg, exp_avg_sq[, slow_buffer])
-        self.m = self.v = None  # flat["exp_avg"], flat["exp_avg_sq"]
+        self.m = self.v = None  # flat["exp_avg"], flat["exp_avg_sq"] (Adam, Ranger)
+        self.device = None
         self.steps = self.ticket = None  # per-parameter update counts (torch counts per parameter)
         self.cap = 0
         self.eager = None       # _Table of the launch-by-launch steps
@@ -92,21 +97,35 @@ class _Plan:
 class _TableStep:
     """What the single-launch optimizers share: per parameter group a `_Plan` (flat state buffers, device step counts, the
     device tables of (parameter, gradient)), the capture bookkeeping and the launches (one group; several groups under a
-    `DeviceGradScaler`: every check first).  The subclass names its flat state (`_flat_keys`), its entry points (`_entry`:
-    <entry>_step, _step_scaled, _check_scaled, _update_scaled), its launch arguments (`_args`) and its CPU form (`_cpu_step`)."""
+    `DeviceGradScaler`: every check first).  The subclass names its flat state (`_flat_keys`, or `_keys(group)` where it depends on
+    the group's hyper-parameters), its entry points (`_entry`: <entry>_step, _step_scaled, _check_scaled, _update_scaled), its
+    launch arguments (`_args`) and its CPU form (`_cpu_step`).  `_step_key`: the state key the device count is published under
+    (None: the count is internal)."""
 
     _flat_keys = ("exp_avg", "exp_avg_sq")
+    _step_key = "step"
     _entry = "srk_adam"
     _sparse_msg = "Adam does not support sparse gradients, please consider SparseAdam instead"
 
     # -- state ------------------------------------------------------------------------------------
+    def _keys(self, group):
+        """The flat state buffers the group's configuration uses (nothing else is allocated, read or written)."""
+        return self._flat_keys
+
+    def _count0(self, st, carried):
+        """The number of updates a tensor has had when a plan adopts it (`st`: its state; `carried`: its count in the plan this one
+        is rebuilt from, or None)."""
+        return float(st.get("step", 0) or 0)                 # (an int or a tensor)
+
     def _plan(self, gi, group):
         plan = self._plans.get(gi)
         params = [p for p in group["params"] if p.requires_grad]
-        if plan is not None and all(p in plan.offsets for p in params):
+        keys = tuple(self._keys(group))
+        if plan is not None and plan.keys == keys and all(p in plan.offsets for p in params):
             return plan
         if not params:
             return None
+        old = plan                                           # rebuilt: a parameter was added, or a hyper-parameter changed the keys
         dev = params[0].device
         for p in params:
             if not p.is_cuda:
@@ -118,8 +137,9 @@ class _TableStep:
         for k, p in enumerate(params):
             plan.offsets[p], plan.index[p] = off, k
             off += (p.numel() + 3) // 4 * 4                 # every tensor starts 16-byte aligned
-        plan.flat = {key: torch.zeros(max(off, 4), dtype=torch.float32, device=dev) for key in self._flat_keys}
-        plan.m, plan.v = plan.flat["exp_avg"], plan.flat["exp_avg_sq"]
+        plan.keys, plan.device = keys, dev
+        plan.flat = {key: torch.zeros(max(off, 4), dtype=torch.float32, device=dev) for key in keys}
+        plan.m, plan.v = plan.flat.get("exp_avg"), plan.flat.get("exp_avg_sq")
         plan.steps = torch.zeros(len(params), dtype=torch.float32, device=dev)
         plan.ticket = torch.zeros(1, dtype=torch.int32, device=dev)
         # table of the largest case (every parameter has a gradient): tensors | 16-byte gap | blocks
@@ -127,16 +147,20 @@ class _TableStep:
         plan.cap = cap
         plan.eager, plan.spare = _Table(cap, dev), _Table(cap, dev)
         host_steps = [0.0] * len(params)
+        old_counts = old.steps.tolist() if old is not None else []
         for k, p in enumerate(params):
+            if not keys and self._step_key is None and p not in self.state:
+                continue                                     # stateless (SGD without momentum): torch keeps no entry either
             st = self.state[p]
             o, n = plan.offsets[p], p.numel()
             views = {key: buf[o:o + n].view_as(p) for key, buf in plan.flat.items()}
-            if "exp_avg" in st:                              # loaded (load_state_dict) or carried-over (add_param_group) state
-                for key, view in views.items():
+            for key, view in views.items():                  # loaded (load_state_dict) or carried-over (a rebuilt plan) state
+                if torch.is_tensor(st.get(key)):
                     view.copy_(st[key])
-                host_steps[k] = float(st.get("step", 0))     # (an int or a tensor)
+            host_steps[k] = self._count0(st, old_counts[old.index[p]] if old is not None and p in old.index else None)
             st.update(views)
-            st["step"] = plan.steps[k]
+            if self._step_key is not None:
+                st[self._step_key] = plan.steps[k]
         if any(host_steps):
             plan.steps.copy_(torch.tensor(host_steps, dtype=torch.float32))
         self._plans[gi] = plan
@@ -160,7 +184,7 @@ class _TableStep:
         for gi, group in enumerate(self.param_groups):
             plan = self._plan(gi, group)
             if plan is not None and plan.spare is None:
-                plan.spare = _Table(plan.cap, plan.m.device)
+                plan.spare = _Table(plan.cap, plan.device)
 
     def release_captured_tables(self):
         """Call after the graphs that captured this optimizer's step have been destroyed (a re-capture): their tables are
@@ -180,12 +204,12 @@ class _TableStep:
             # fallbacks) keep using `plan.eager`
             # (no spare: the caller did not `reserve_capture_tables()`; the page-locked allocation below only succeeds in a
             # relaxed-mode capture)
-            t, plan.spare = (plan.spare or _Table(plan.cap, plan.m.device)), None
+            t, plan.spare = (plan.spare or _Table(plan.cap, plan.device)), None
             plan.captured.append(t)
         else:
             t = plan.eager
             if plan.spare is None:
-                plan.spare = _Table(plan.cap, plan.m.device)
+                plan.spare = _Table(plan.cap, plan.device)
             if key == t.key:
                 return t
         for p, g in live:
@@ -252,7 +276,7 @@ class _TableStep:
             plan = self._plan(gi, group)
             if plan is None:
                 continue
-            with torch.cuda.device(plan.m.device):
+            with torch.cuda.device(plan.device):
                 t = self._table(plan, group)
                 if t.nblocks == 0:
                     continue
@@ -263,10 +287,10 @@ class _TableStep:
         split = grad_scaler is not None and len(launches) > 1
         if split:
             for plan, t, a in launches:
-                with torch.cuda.device(plan.m.device):
+                with torch.cuda.device(plan.device):
                     L.check(getattr(lib, e + "_check_scaled")(C.byref(a), grad_scaler.state.data_ptr(), torch.cuda.current_stream().cuda_stream), e + "_check_scaled")
         for plan, t, a in launches:
-            with torch.cuda.device(plan.m.device):
+            with torch.cuda.device(plan.device):
                 stream = torch.cuda.current_stream().cuda_stream
                 if grad_scaler is None:
                     L.call(e + "_step", a, stream)
@@ -318,6 +342,112 @@ class Adam(_TableStep, torch.optim.Adam):
     def _cpu_step(self, closure):
         return torch.optim.Adam.step(self, closure)
 
+
+def _reject_unsupported(name, lr, differentiable, fused=None):
+    if isinstance(lr, torch.Tensor):
+        raise NotImplementedError(f"a tensor lr is not implemented by the HIP {name} (the launch takes lr by value)")
+    if differentiable:
+        raise NotImplementedError(f"differentiable=True is not implemented by the HIP {name}")
+    if fused:
+        raise NotImplementedError(f"fused=True is not implemented by the HIP {name} (its step is one HIP launch already)")
+
+
+class SGD(_TableStep, torch.optim.SGD):
+    """torch.optim.SGD(params, lr, momentum, dampening, weight_decay, nesterov, maximize=...) with a single-launch step
+    (`srk_sgd_step`) for GPU parameters.  torch's constructor and its validation; `foreach` is accepted and has no effect on the
+    GPU; `differentiable=True`, `fused=True` and a tensor `lr` raise NotImplementedError.
+
+    State: none with `momentum == 0` (12 B of traffic per parameter), else `momentum_buffer` (20 B) -- torch's keys, and a
+    `state_dict()` that loads into torch.optim.SGD and back.  torch creates a tensor's `momentum_buffer` as a copy of the first
+    gradient it ever receives, ignoring `dampening`; "has this tensor had a step" is a per-tensor count ON THE DEVICE (so a
+    replayed hipGraph and a step skipped by the loss scaler get it right) that never appears in `state` or `state_dict()`.
+    The buffers are views into one flat buffer: `opt.state[p]["momentum_buffer"]` is a live tensor from the first GPU step of
+    the optimizer on, and its content is MEANINGLESS until `p` has had its own first step; `state_dict()` exports None for such
+    a tensor (it reads the counts on the host: not on the step's path), and `load_state_dict` sets the count to 1 where it is
+    given a tensor and to 0 where it finds None or nothing.
+
+    CPU parameters step through torch.optim.SGD.step itself."""
+
+    _step_key = None
+    _entry = "srk_sgd"
+    _sparse_msg = "sr-pytorch-lightning_amd.optim.SGD does not support sparse gradients"
+
+    def __init__(self, params, lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=False, *, maximize=False, foreach=None,
+                 differentiable=False, fused=None):
+        _reject_unsupported("SGD", lr, differentiable, fused)
+        super().__init__(params, lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov,
+                         maximize=maximize, foreach=foreach, differentiable=False, fused=fused)
+        self._plans = {}
+
+    def _keys(self, group):
+        return ("momentum_buffer",) if group["momentum"] != 0 else ()
+
+    def _count0(self, st, carried):
+        if carried is not None:
+            return carried
+        return 1.0 if torch.is_tensor(st.get("momentum_buffer")) else 0.0    # loaded: torch has a buffer from the first step on
+
+    def state_dict(self):
+        sd = super().state_dict()
+        idx = 0
+        for gi, group in enumerate(self.param_groups):
+            plan = self._plans.get(gi)
+            counts = plan.steps.tolist() if plan is not None and plan.keys else None
+            for p in group["params"]:
+                if counts is not None and p in plan.index and counts[plan.index[p]] == 0 and idx in sd["state"]:
+                    sd["state"][idx] = dict(sd["state"][idx], momentum_buffer=None)      # torch: no buffer before the first step
+                idx += 1
+        return sd
+
+    def _args(self, plan, t, group):
+        mom = float(group["momentum"])
+        return L.SgdArgs(slots=t.table.data_ptr(), blocks=t.table.data_ptr() + t.blocks_off, nslots=t.nslots, nblocks=t.nblocks,
+                         buf=plan.flat["momentum_buffer"].data_ptr() if mom != 0 else None, steps=plan.steps.data_ptr(),
+                         lr=float(group["lr"]), momentum=mom, dampening=float(group["dampening"]),
+                         weight_decay=float(group["weight_decay"]), nesterov=int(bool(group["nesterov"])),
+                         maximize=int(bool(group["maximize"])))
+
+    def _cpu_step(self, closure):
+        for group in self.param_groups:
+            if any(p.grad is not None and p.grad.is_sparse for p in group["params"]):
+                raise RuntimeError(self._sparse_msg)
+        return torch.optim.SGD.step(self, closure)
+
+
+class RMSprop(_TableStep, torch.optim.RMSprop):
+    """torch.optim.RMSprop(params, lr, alpha, eps, weight_decay, momentum, centered, ...) with a single-launch step
+    (`srk_rmsprop_step`) for GPU parameters.  torch's constructor and its validation; `capturable` / `foreach` are accepted and
+    have no effect on the GPU (the step count always lives on the device); `differentiable=True` and a tensor `lr` raise
+    NotImplementedError.
+
+    State: torch's keys for the configuration -- `step`, `square_avg`, `momentum_buffer` iff `momentum > 0`, `grad_avg` iff
+    `centered` -- as views into flat buffers; only those buffers exist and are touched (20 B of traffic per parameter, +8 B with
+    momentum, +8 B centered).  `state_dict()` loads into torch.optim.RMSprop and back; `load_state_dict` takes CPU tensors and
+    integer or tensor steps.  CPU parameters step through torch.optim.RMSprop.step itself."""
+
+    _entry = "srk_rmsprop"
+    _sparse_msg = "RMSprop does not support sparse gradients"
+
+    def __init__(self, params, lr=1e-2, alpha=0.99, eps=1e-8, weight_decay=0, momentum=0, centered=False, capturable=False,
+                 foreach=None, maximize=False, differentiable=False):
+        _reject_unsupported("RMSprop", lr, differentiable)
+        super().__init__(params, lr=lr, alpha=alpha, eps=eps, weight_decay=weight_decay, momentum=momentum, centered=centered,
+                         capturable=capturable, foreach=foreach, maximize=maximize, differentiable=False)
+        self._plans = {}
+
+    def _keys(self, group):
+        return ("square_avg",) + (("momentum_buffer",) if group["momentum"] > 0 else ()) + (("grad_avg",) if group["centered"] else ())
+
+    def _args(self, plan, t, group):
+        ptr = {key: buf.data_ptr() for key, buf in plan.flat.items()}
+        return L.RmspropArgs(slots=t.table.data_ptr(), blocks=t.table.data_ptr() + t.blocks_off, nslots=t.nslots, nblocks=t.nblocks,
+                             sq=ptr["square_avg"], buf=ptr.get("momentum_buffer"), ga=ptr.get("grad_avg"), steps=plan.steps.data_ptr(),
+                             lr=float(group["lr"]), alpha=float(group["alpha"]), eps=float(group["eps"]),
+                             weight_decay=float(group["weight_decay"]), momentum=float(group["momentum"]),
+                             centered=int(bool(group["centered"])), maximize=int(bool(group["maximize"])))
+
+    def _cpu_step(self, closure):
+        return torch.optim.RMSprop.step(self, closure)
 
 
 

@@ -261,7 +261,7 @@ def _eager_step(model, net, optimizer, gsync, scaler, batch):
         if gsync is not None:
             gsync.sync()
         optimizer.step(grad_scaler=scaler)
-    elif scaler is not None:                                  # torch.amp.GradScaler (an optimizer that is not the HIP Adam or Ranger)
+    elif scaler is not None:                                  # torch.amp.GradScaler (an optimizer that is not one of optim.py's)
         scaler.scale(loss).backward()
         ops.flush_wgrads()
         if gsync is not None:
@@ -313,14 +313,16 @@ class GraphedStep:
     def _hyper(self):
         """The optimizer's hyper-parameters travel BY VALUE in the captured launch (srk_adam_args): a scheduler or a manual
         change after the capture would be ignored by a replay, so a change re-captures."""
-        keys = ("lr", "betas", "eps", "weight_decay", "maximize", "momentum", "alpha", "k", "N_sma_threshhold")
+        keys = ("lr", "betas", "eps", "weight_decay", "maximize", "momentum", "dampening", "nesterov", "alpha", "centered", "k",
+                "N_sma_threshhold")
         return tuple(tuple((k, tuple(g[k]) if isinstance(g[k], (tuple, list)) else float(g[k])) for k in keys if k in g)
                      for g in self.opt.param_groups)
 
     def _set_hyper(self, snap):
         for g, vals in zip(self.opt.param_groups, snap):
             for k, v in vals:
-                g[k] = tuple(v) if isinstance(v, tuple) else int(v) if k == "k" else v      # (Ranger's Lookahead period is an int)
+                # (Ranger's Lookahead period is an int; the flags are booleans: the snapshot holds them as floats)
+                g[k] = tuple(v) if isinstance(v, tuple) else int(v) if k == "k" else bool(v) if k in ("maximize", "nesterov", "centered") else v
 
     def _mark_pending(self):
         self.pending, self.pending_hyper = True, self._hyper()
@@ -729,9 +731,10 @@ class Trainer:
             use_scaler = getattr(model, "compute_dtype", torch.float32) == torch.float16 and self.device.type == "cuda"
         if use_scaler:
             # fp16 (the reference's `precision: 16` = Lightning "16-mixed": autocast + GradScaler, configs/all.yml:122): dynamic loss
-            # scaling with its state on the device when the optimizer is the HIP Adam or Ranger, so that the step can still be a hipGraph
-            from .optim import Adam as _HipAdam, DeviceGradScaler, Ranger as _HipRanger
-            scaler = DeviceGradScaler(self.device) if isinstance(optimizer, (_HipAdam, _HipRanger)) else torch.amp.GradScaler("cuda")
+            # scaling with its state on the device when the optimizer is one of optim.py's single-launch steps (Adam, Ranger, SGD,
+            # RMSprop), so that the step can still be a hipGraph
+            from .optim import DeviceGradScaler, _TableStep
+            scaler = DeviceGradScaler(self.device) if isinstance(optimizer, _TableStep) else torch.amp.GradScaler("cuda")
         self.scaler = scaler
         graphed = None
         if self.use_graph and (scaler is None or hasattr(scaler, "state")) and self.device.type == "cuda" and not use_ddp:
