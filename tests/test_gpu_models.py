@@ -8,12 +8,15 @@ reference with the looser bounds below, and by PSNR(build, reference) > 50 dB on
 """
 import json
 import os
+import sys
 
 import numpy as np
 import pytest
 import torch
 
 from oracle import fill, functional as OF, init as OI
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))          # tests/eval_ref.py
 
 pytestmark = pytest.mark.gpu
 
@@ -260,22 +263,20 @@ def test_fused_adam_training_sees_updated_weights(A):
 @pytest.mark.parametrize("dt,min_psnr", [(torch.float32, 90.0), (torch.bfloat16, 50.0)])
 def test_full_image_inference_vs_oracle(A, dt, min_psnr):
     """validation/predict path (srmodel.py:214-232,375-433): batch 1, arbitrary H x W (not multiples of the 16x16
-    tile), clamp + uint8 rounding; EDSR-baseline at default init against the fp32 CPU oracle."""
-    ent = MANIFEST["edsr_baseline_x4"]
-    torch.manual_seed(0)
-    m = A.EDSR(precision=PREC[dt], **ent["kwargs"])
-    sd = {k: v.detach().clone() for k, v in m.state_dict().items()}
-    m = m.cuda().eval()
+    tile), clamp + uint8 rounding; EDSR-baseline at default init against the float64 CPU oracle, through the one implementation of
+    "compare a whole image with the oracle" (tests/eval_ref.py), which adds its own bounds and the position checks to the ones here."""
+    import eval_ref as ER
+    case = ER.BY_ID["edsr_x4_85x123"]
+    assert case.kw == MANIFEST["edsr_baseline_x4"]["kwargs"]
     x = torch.rand(1, 3, 85, 123, generator=torch.Generator().manual_seed(7))
-    with torch.no_grad():
-        y_ref = OF.forward("EDSR", sd, x, **ent["kwargs"]).clamp(0, 1)
-        y = m.predict_step({"lr": x.cuda()}, 0)
+    ref = ER.RefCache(A).get(case, x)
+    m, y = ER.compare_predict(A, ref, dt)
     assert tuple(y.shape) == (1, 3, 340, 492)
-    mse = float(((y.cpu().double() - y_ref.double()) ** 2).mean())
+    mse = float(((y.cpu().double() - ref.ref.double()) ** 2).mean())
     psnr = 10 * np.log10(1.0 / max(mse, 1e-30))
     assert psnr > min_psnr, f"PSNR(build, oracle) = {psnr:.1f} dB"
     # uint8 rounding (torchvision.utils.save_image): identical except where the fp32 values straddle x.5/255
-    d = (m.to_uint8(y).cpu().int() - m.to_uint8(y_ref).int()).abs()
+    d = (m.to_uint8(y).cpu().int() - m.to_uint8(ref.ref.float()).int()).abs()
     assert int(d.max()) <= 1 and float((d > 0).float().mean()) < (1e-3 if dt == torch.float32 else 0.08)
 
 
