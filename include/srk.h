@@ -883,6 +883,37 @@ int srk_rmsprop_step_scaled(const srk_rmsprop_args* a, float* scaler_state, srk_
 int srk_rmsprop_check_scaled(const srk_rmsprop_args* a, float* scaler_state, srk_stream_t stream);
 int srk_rmsprop_update_scaled(const srk_rmsprop_args* a, const float* scaler_state, srk_stream_t stream);
 
+/* ---- tiled and self-ensemble inference (tiling.py), csrc/tile.hip -------------------------------------------------------------
+ * The two data movements around the model's forward when a large image is predicted as a batch of overlapping tiles and / or as the
+ * mean over the 8 flips and transposes of the input.  Transform id k: bit 0 reverses W, bit 1 reverses H, bit 2 transposes H and W
+ * after the flips.  A tile lives in the TRANSFORMED frame: pixel (Y, X) of transform_k(image) is pixel (y, x) of the image with
+ *     (y1, x1) = bit 2 ? (X, Y) : (Y, X);   y = bit 1 ? H-1-y1 : y1;   x = bit 0 ? W-1-x1 : x1.
+ * srk_tile_gather: dst[n][c][i][j] = transform_id(src)[c][y0 + i][x0 + j] for the N entries of the DEVICE table, src the LR image
+ *   [1][C][H][W], dst the batch [N][C][th][tw]; every tile must lie inside the transformed image.
+ * srk_tile_place: src is the batch of SR tiles [N][C][scale*th][scale*tw] (tile n covers rows scale*y0 ..., columns scale*x0 ... of the
+ *   transformed HR frame), dst the HR image [1][C][scale*H][scale*W].  Every pixel (y, x) of entry n's owned rectangle
+ *   [oy, oy+oh) x [ox, ox+ow) -- given in the UNTRANSFORMED HR image -- receives the tile's value at the matching frame position:
+ *   dst = v (accumulate == 0) or dst = dst + weight * v (accumulate != 0: rectangles of one launch must not overlap).  max_oh / max_ow:
+ *   the largest oh / ow of the table's entries (host-known; sizes the grid).
+ * Both are fp32 NCHW, one launch for any N, 64-bit element offsets (the HR image may pass 2^31 elements). */
+typedef struct {
+  int y0, x0;                             /* tile origin in the transformed LR frame                        */
+  int id;                                 /* transform 0..7                                                 */
+  int oy, ox, oh, ow;                     /* place: owned rectangle in the untransformed HR image           */
+  int pad_;
+} srk_tile_desc;
+typedef struct {
+  const float* src; float* dst;
+  const srk_tile_desc* table;             /* [N] on the device                                              */
+  int N, C, H, W;                         /* entries; channels and sides of the (untransformed) LR image    */
+  int th, tw;                             /* LR tile sides in the transformed frame                         */
+  int scale;                              /* place                                                          */
+  int max_oh, max_ow;                     /* place                                                          */
+  int accumulate; float weight;           /* place                                                          */
+} srk_tile_args;
+int srk_tile_gather(const srk_tile_args* a, srk_stream_t stream);
+int srk_tile_place(const srk_tile_args* a, srk_stream_t stream);
+
 /* ---- misc ------------------------------------------------------------------------------------------ */
 const char* srk_last_error(void);
 int srk_version(void);

@@ -33,8 +33,13 @@ def main(argv=None):
     p.add_argument("--n_resblocks", type=int, default=None)
     p.add_argument("--n_resgroups", type=int, default=None)
     p.add_argument("--res_scale", type=float, default=None)
+    p.add_argument("--tile", type=int, default=None, help="LR tile side of tiled inference (0: whole image)")
+    p.add_argument("--tile_pad", type=int, default=None, help="LR pixels of context around what a tile owns")
+    p.add_argument("--tile_batch", type=int, default=None, help="tiles per forward")
+    p.add_argument("--self_ensemble", action="store_true", default=None, help="mean over the 8 flips / transposes of the input")
     a = p.parse_args(argv)
-    kw = {k: getattr(a, k) for k in ("n_feats", "n_resblocks", "n_resgroups", "res_scale") if getattr(a, k) is not None}
+    kw = {k: getattr(a, k) for k in ("n_feats", "n_resblocks", "n_resgroups", "res_scale", "tile", "tile_pad", "tile_batch", "self_ensemble")
+          if getattr(a, k) is not None}
     names = {m.lower(): m for m in sr_amd.models.__all__ if m != "SRModel"}
     cls = getattr(sr_amd, names[a.model.lower()])
     ds_names = [os.path.basename(os.path.normpath(d)) for d in a.predict_datasets]

@@ -257,6 +257,15 @@ class HrTailArgs(C.Structure):
                 ("r", _p), ("r0", _p), ("dwt", _p), ("dbt", _p), ("dwu", _p), ("dbu", _p)]
 
 
+class TileDesc(C.Structure):
+    _fields_ = [("y0", _i), ("x0", _i), ("id", _i), ("oy", _i), ("ox", _i), ("oh", _i), ("ow", _i), ("pad_", _i)]
+
+
+class TileArgs(C.Structure):
+    _fields_ = [("src", _p), ("dst", _p), ("table", _p), ("N", _i), ("C", _i), ("H", _i), ("W", _i), ("th", _i), ("tw", _i),
+                ("scale", _i), ("max_oh", _i), ("max_ow", _i), ("accumulate", _i), ("weight", _f)]
+
+
 # every launcher declared in include/srk.h: name -> argument struct
 LAUNCHERS = {
     "srk_pack_conv_weights": PackArgs,
@@ -302,6 +311,8 @@ LAUNCHERS = {
     "srk_hrtail_edge_bwd_x": HrTailArgs,
     "srk_hrtail_edge_bwd_w": HrTailArgs,
     "srk_hrtail_expand": HrTailArgs,
+    "srk_tile_gather": TileArgs,
+    "srk_tile_place": TileArgs,
 }
 OTHER_SYMBOLS = ("srk_conv_tile", "srk_last_error", "srk_version", "srk_device_cus", "srk_wgrad_slabs",
                  "srk_pack_conv_weights_group", "srk_l1_blocks", "srk_wgrad_group_ok", "srk_wgrad_group_job_bytes",

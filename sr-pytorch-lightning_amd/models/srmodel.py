@@ -20,6 +20,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import optim as _hip_optim
+from .. import tiling as _tiling
 
 try:  # pragma: no cover - lightning is not installed in the build image
     import lightning.pytorch as pl
@@ -231,6 +232,10 @@ class SRModel(_Base):
                  save_results: int = -1,
                  save_results_from_epoch: str = 'last',
                  scale_factor: int = 4,
+                 tile: int = 0,
+                 tile_pad: int = _tiling.DEFAULT_TILE_PAD,
+                 tile_batch: int = _tiling.DEFAULT_TILE_BATCH,
+                 self_ensemble: bool = False,
                  **kwargs: dict[str, Any]):
         super().__init__()
         self._logger = logging.getLogger(__name__)
@@ -260,6 +265,10 @@ class SRModel(_Base):
         self._scale_factor = scale_factor
         self._training_step_outputs = []
         self._validation_step_outputs = []
+        #: tiled / x8 self-ensemble evaluation (tiling.py): `tile` is the LR tile side (0: off), `tile_pad` the LR pixels of context a
+        #: tile carries beyond what it owns, `tile_batch` how many tiles one forward takes; both off is the whole-image path
+        _tiling.check_args(tile, tile_pad, tile_batch)
+        self._tile, self._tile_pad, self._tile_batch, self._self_ensemble = tile, tile_pad, tile_batch, bool(self_ensemble)
         #: arithmetic type of the HIP path: storage dtype of activations / packed weights (fp32 accumulate)
         self.compute_dtype = _dtype_from_precision(precision)
         #: storage dtype of the validation / predict forward.  bf16 keeps 8 mantissa bits on the residual trunk, which
@@ -299,6 +308,8 @@ class SRModel(_Base):
 
     def _eval_forward(self, x):
         """`forward` in the evaluation storage dtype (see `eval_dtype`)."""
+        if self._tile or self._self_ensemble:
+            return self._eval_forward_tiled(x)
         if self.eval_dtype == self.compute_dtype or not x.is_cuda:
             return self.forward(x)
         prev, self.compute_dtype = self.compute_dtype, self.eval_dtype
@@ -308,6 +319,22 @@ class SRModel(_Base):
             self.compute_dtype = prev
         if self.eval_dtype == torch.float16 and not bool(torch.isfinite(y).all()):
             y = self.forward(x)                   # fp16 range exceeded: the training dtype's answer
+        return y
+
+    def _eval_forward_tiled(self, x):
+        """`_eval_forward` through tiling.tiled_forward: the same dtype rule, applied to the assembled image (one sync)."""
+        def run():
+            return _tiling.tiled_forward(self.forward, x, self._scale_factor, tile=self._tile, pad=self._tile_pad,
+                                         tile_batch=self._tile_batch, self_ensemble=self._self_ensemble)
+        if self.eval_dtype == self.compute_dtype or not x.is_cuda:
+            return run()
+        prev, self.compute_dtype = self.compute_dtype, self.eval_dtype
+        try:
+            y = run()
+        finally:
+            self.compute_dtype = prev
+        if self.eval_dtype == torch.float16 and not bool(torch.isfinite(y).all()):
+            y = run()                             # fp16 range exceeded: the training dtype's answer
         return y
 
     # -- srmodel.py:214-232 (metric core; image dumping is out of scope) ----------------------------
