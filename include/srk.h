@@ -543,6 +543,32 @@ int srk_haarpsi_fwd(const srk_haarpsi_args* a, srk_stream_t stream);
 int srk_haarpsi_finalize(const srk_haarpsi_args* a, srk_stream_t stream);
 int srk_haarpsi_bwd(const srk_haarpsi_args* a, srk_stream_t stream);
 
+/* ---- SSIM loss (piq.SSIMLoss with piq.ssim's defaults; "0.16*l1+0.84*ssim" of Zhao et al. 2017), csrc/ssim_loss.hip --------------
+ * x = clamp(sr, 0, 1) (test), y = hr (reference).  Both are average-pooled by f = max(1, round(min(H, W) / 256)) (Python's round;
+ * Hp = H / f, Wp = W / f, remainder rows / columns dropped), filtered with the separable 11-tap Gaussian (sigma 1.5) over the
+ * valid (Hp-10) x (Wp-10) map: S = (2 mu_x mu_y + c1)(2 s_xy + c2) / ((mu_x^2 + mu_y^2 + c1)(s_xx + s_yy + c2)), c1 = 1e-4,
+ * c2 = 9e-4; loss = 1 - mean of S over the map, the channels and the images (srk_image_ssim's value on in-range input).
+ * Forward: one workgroup per (plane, 16x16 map tile) -> one double per tile in its own slot (no atomics).  Finalize: one workgroup,
+ * the fixed-order fp64 sum -> loss.  Backward: one workgroup per (plane, 16x32 pooled-pixel tile) recomputes the moments on a
+ * 10-pixel halo from sr and hr, d loss / d sr times *gout (device scalar: no host sync), each pixel of an f x f block taking
+ * 1 / f^2 of its pooled pixel's gradient, zero where sr lies outside [0, 1].  The dropped remainder rows / columns of grad are
+ * NOT written: the caller zeroes them.  hr gets no gradient and is not range-checked.  NCHW fp32, any C >= 1, Hp, Wp >= 11,
+ * N * C * (tiles per plane) < 2^31. ------------------------------------------------------------------------------------------- */
+typedef struct srk_ssim_loss_args {
+  const float* sr;                        /* test image [N][C][H][W] (forward, backward; clamped on load)                    */
+  const float* hr;                        /* reference image [N][C][H][W] (forward, backward)                                */
+  int N, C, H, W;
+  double* partial;                        /* [srk_ssim_loss_tiles(N, C, H, W)]: per forward tile, the sum of S               */
+  float* loss;                            /* finalize: device scalar 1 - SSIM                                                */
+  const float* gout;                      /* backward: device scalar                                                         */
+  float* grad;                            /* backward: [N][C][H][W] d loss / d sr                                            */
+} srk_ssim_loss_args;
+/* forward tiles over the whole batch (N * C planes x tiles per plane), or -1 when the sizes are refused */
+int srk_ssim_loss_tiles(int N, int C, int H, int W);
+int srk_ssim_loss_fwd(const srk_ssim_loss_args* a, srk_stream_t stream);
+int srk_ssim_loss_finalize(const srk_ssim_loss_args* a, srk_stream_t stream);
+int srk_ssim_loss_bwd(const srk_ssim_loss_args* a, srk_stream_t stream);
+
 /* ---- SSIM with piq.ssim's defaults (reference srmodel.py:52-53,567-593 -> piq.ssim): images are average-pooled by
  * `pool` = max(1, round(min(H, W) / 256)) (floor division of the extent, as F.avg_pool2d), filtered with the separable
  * 11-tap Gaussian (sigma), and the SSIM map of the VALID region ((Hp-10) x (Wp-10)) is summed per (image, channel)

@@ -80,8 +80,16 @@ def _haarpsi_loss(sr, hr):
     return haarpsi.haarpsi_loss(sr, hr)
 
 
+def _ssim_loss(sr, hr):
+    """piq.SSIMLoss with piq.ssim's defaults, called like the other piq losses on clamp(sr, 0, 1) and hr: 1 - SSIM, the structural
+    term of "0.16*l1+0.84*ssim" (Zhao et al. 2017); on the GPU the fused HIP forward/backward (ssim_loss.SSIMLossFn, which clamps
+    inside), elsewhere ssim_loss.ssim_torch.  On in-range images the value is 1 - _ssim(sr, hr)."""
+    from .. import ssim_loss
+    return ssim_loss.ssim_loss(sr, hr)
+
+
 _supported_losses = {"l1": _l1_loss, "l2": F.mse_loss, "mae": _l1_loss, "mse": F.mse_loss, "flip": _flip_loss,
-                     "haarpsi": _haarpsi_loss}
+                     "haarpsi": _haarpsi_loss, "ssim": _ssim_loss}
 _out_of_scope_losses = {"adaptive", "dists", "edge_loss", "lpips", "pencil_sketch", "pieapp"}
 
 # models/srmodel.py:57-64

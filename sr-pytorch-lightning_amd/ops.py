@@ -1508,3 +1508,4 @@ from .ops_proj import _proj_launch      # noqa: E402,F401  (bench.py / tools/mic
 from .ops_metrics import *   # noqa: E402,F401,F403  PSNR / SSIM reductions, L1 loss
 from .flip import *          # noqa: E402,F401,F403  FLIP loss and metric (csrc/flip.hip)
 from .haarpsi import *       # noqa: E402,F401,F403  HaarPSI loss (csrc/haarpsi.hip)
+from .ssim_loss import *     # noqa: E402,F401,F403  SSIM loss (csrc/ssim_loss.hip)
