@@ -569,6 +569,45 @@ int srk_ssim_loss_fwd(const srk_ssim_loss_args* a, srk_stream_t stream);
 int srk_ssim_loss_finalize(const srk_ssim_loss_args* a, srk_stream_t stream);
 int srk_ssim_loss_bwd(const srk_ssim_loss_args* a, srk_stream_t stream);
 
+/* ---- MS-SSIM loss (piq.MultiScaleSSIMLoss with piq.multi_scale_ssim's defaults; "0.16*l1+0.84*ms_ssim" of Zhao et al. 2017),
+ * csrc/ms_ssim_loss.hip.  x = clamp(sr, 0, 1) (test), y = hr (reference); the pyramid, the maps and the per-level means cs_k, ss_k
+ * are srk_ms_ssim's (below).  m_k = cs_k (k < 4), m_4 = ss_4; per (image, channel) plane v = prod_k max(m_k, 0)^w_k with the weights
+ * 0.0448, 0.2856, 0.3001, 0.2363, 0.1333; loss = 1 - mean of v over channels and images.  H, W >= 161, H * W <= 2^24, any C >= 1,
+ * N * C * (blocks per plane of any launch) < 2^31: anything else is refused with -1.
+ * Forward: four pooling launches (the clamp of sr folded into the reads of level 0) fill `workspace` with levels 1-4 of both images,
+ * then one launch over the 16x16 map tiles of all five levels writes (sum ss, sum cs) per tile to a fixed slot of `partials`.
+ * Finalize: one workgroup, fixed-order fp64 sums -> `loss`, and table[plane][k] = w_k v / (m_k count_k N C), the factor the backward
+ * scales level k's adjoint by; all five are 0 for a plane with any m_k <= 0 (v = 0 there; piq's relu(m)^w has an infinite slope at 0
+ * and its autograd returns NaN: here such a plane gets a zero gradient).
+ * Backward: one launch per level, level 4 first.  One workgroup per (plane, 16x32 pixel tile of level k) recomputes the moments on a
+ * 10-pixel halo from the pyramid, applies the transposed filter to the adjoint of cs (ss at level 4) times -table[plane][k],
+ * adds 1/4 of the gradient of its parent pixel ((i + p) / 2, (j + p) / 2) of level k+1 (nothing when
+ * that lies outside level k+1: the row / column the pooling's floor drops; twice that share on row / column 0 when p = 1: the
+ * replicated pad) and writes level k's gradient once, levels 1-4 (per unit of the upstream gradient) into `gwork`, level 0 times
+ * *gout (device scalar: no host sync; applied once, so grad is linear in it to the last bit) under the clamp's mask (zero where sr
+ * lies outside [0, 1]) into `grad`.  Gather form: no atomics; bit-reproducible.  hr gets no gradient and is not range-checked.
+ * NCHW fp32.  `workspace`, `table` and sr / hr must be the forward's when the backward runs. ----------------------------------- */
+typedef struct srk_ms_ssim_loss_args {
+  const float* sr;                        /* test image [N][C][H][W] (forward, backward; clamped on load)                    */
+  const float* hr;                        /* reference image [N][C][H][W] (forward, backward)                                */
+  int N, C, H, W;
+  float* workspace;                       /* srk_ms_ssim_loss_workspace_bytes(N, C, H, W) bytes: levels 1-4 of both images   */
+  double* partials;                       /* [N*C][srk_ms_ssim_loss_tiles(...)][2], 16-byte aligned: (sum ss, sum cs)        */
+  float* table;                           /* [N*C][5]: finalize writes, backward reads                                       */
+  float* loss;                            /* finalize: device scalar 1 - MS-SSIM                                             */
+  const float* gout;                      /* backward: device scalar                                                         */
+  float* gwork;                           /* backward: half the workspace's bytes, the gradients of levels 1-4 of x          */
+  float* grad;                            /* backward: [N][C][H][W] d loss / d sr                                            */
+} srk_ms_ssim_loss_args;
+/* bytes of the pyramid workspace (a multiple of 256; srk_ms_ssim_workspace_bytes' value), or -1 when the sizes are refused */
+long long srk_ms_ssim_loss_workspace_bytes(int N, int C, int H, int W);
+/* map tiles per plane over all five levels (srk_ms_ssim_tiles' value), or -1 when the sizes are refused; first (nullable)
+ * receives the 6 level boundaries */
+int srk_ms_ssim_loss_tiles(int N, int C, int H, int W, int* first);
+int srk_ms_ssim_loss_fwd(const srk_ms_ssim_loss_args* a, srk_stream_t stream);
+int srk_ms_ssim_loss_finalize(const srk_ms_ssim_loss_args* a, srk_stream_t stream);
+int srk_ms_ssim_loss_bwd(const srk_ms_ssim_loss_args* a, srk_stream_t stream);
+
 /* ---- SSIM with piq.ssim's defaults (reference srmodel.py:52-53,567-593 -> piq.ssim): images are average-pooled by
  * `pool` = max(1, round(min(H, W) / 256)) (floor division of the extent, as F.avg_pool2d), filtered with the separable
  * 11-tap Gaussian (sigma), and the SSIM map of the VALID region ((Hp-10) x (Wp-10)) is summed per (image, channel)

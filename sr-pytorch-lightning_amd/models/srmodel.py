@@ -88,8 +88,17 @@ def _ssim_loss(sr, hr):
     return ssim_loss.ssim_loss(sr, hr)
 
 
+def _ms_ssim_loss(sr, hr):
+    """piq.MultiScaleSSIMLoss with piq.multi_scale_ssim's defaults, called like the other piq losses on clamp(sr, 0, 1) and hr:
+    1 - MS-SSIM, the structural term of "0.16*l1+0.84*ms_ssim" (Zhao et al. 2017); on the GPU the fused HIP forward/backward
+    (ms_ssim_loss.MSSSIMLossFn, which clamps inside), elsewhere ms_ssim_loss.ms_ssim_torch.  Needs an HR patch of at least 161."""
+    from .. import ms_ssim_loss
+    return ms_ssim_loss.ms_ssim_loss(sr, hr)
+
+
 _supported_losses = {"l1": _l1_loss, "l2": F.mse_loss, "mae": _l1_loss, "mse": F.mse_loss, "flip": _flip_loss,
-                     "haarpsi": _haarpsi_loss, "ssim": _ssim_loss}
+                     "haarpsi": _haarpsi_loss, "ssim": _ssim_loss, "ms_ssim": _ms_ssim_loss}
+_MS_SSIM_MIN_PATCH = 161          # ops_metrics.MS_SSIM_MIN_SIZE: (11 - 1) * 2^4 + 1
 _out_of_scope_losses = {"adaptive", "dists", "edge_loss", "lpips", "pencil_sketch", "pieapp"}
 
 # models/srmodel.py:57-64
@@ -445,6 +454,9 @@ class SRModel(_Base):
                                           f'(SURVEY.md section 2 row 12). Supported: {", ".join(_supported_losses)}')
             else:
                 raise AttributeError(f'Couldn\'t find loss {loss_type}. Supported losses: {", ".join(_supported_losses)}')
+            if loss_type == "ms_ssim" and patch_size < _MS_SSIM_MIN_PATCH:
+                raise ValueError(f'loss ms_ssim needs an HR patch of at least {_MS_SSIM_MIN_PATCH} (five levels of an 11-tap filter), '
+                                 f'got patch_size={patch_size}')
             losses.append(_SubLoss(name=loss_type, loss=fn, weight=weight))
         return losses
 

@@ -1509,3 +1509,4 @@ from .ops_metrics import *   # noqa: E402,F401,F403  PSNR / SSIM reductions, L1 
 from .flip import *          # noqa: E402,F401,F403  FLIP loss and metric (csrc/flip.hip)
 from .haarpsi import *       # noqa: E402,F401,F403  HaarPSI loss (csrc/haarpsi.hip)
 from .ssim_loss import *     # noqa: E402,F401,F403  SSIM loss (csrc/ssim_loss.hip)
+from .ms_ssim_loss import *  # noqa: E402,F401,F403  MS-SSIM loss (csrc/ms_ssim_loss.hip)
