@@ -608,6 +608,37 @@ int srk_ms_ssim_loss_fwd(const srk_ms_ssim_loss_args* a, srk_stream_t stream);
 int srk_ms_ssim_loss_finalize(const srk_ms_ssim_loss_args* a, srk_stream_t stream);
 int srk_ms_ssim_loss_bwd(const srk_ms_ssim_loss_args* a, srk_stream_t stream);
 
+/* ---- GMSD loss and metric (gradient magnitude similarity deviation, Xue, Zhang, Mou, Bovik 2014; piq.GMSDLoss), csrc/gmsd.hip -----
+ * x = clamp(sr, 0, 1) (test), y = hr (reference), C = 1 or 3.  Luma Y = 0.299 R + 0.587 G + 0.114 B (C = 3) or the plane (C = 1);
+ * p = max(H % 2, W % 2) rows / columns of zeros at the bottom / right, then the 2x2 stride-2 average (floor): Hd = (H + p) / 2,
+ * Wd = (W + p) / 2; Prewitt taps [[-1, 0, 1]] x 3 / 3 and their transpose as a cross-correlation with zero padding 1;
+ * a = |grad x|, b = |grad y|, GMS = (2ab + c) / (a^2 + b^2 + c), c = 170 / 255^2; GMSD_n = the population standard deviation of GMS
+ * over the Hd x Wd positions of image n; loss = mean over n of GMSD_n (0 is a perfect match).
+ * Forward: one workgroup per (image, 16x32 tile of the pooled map) stages the pooled luma of both images with a 1-position halo in
+ * LDS and writes (sum d, sum d^2) of d = GMS - 1 = -(a - b)^2 / (a^2 + b^2 + c) as two doubles into its own slot (no atomics).
+ * Finalize: per image the fixed-order fp64 sums -> stats[n] = (mean of d, GMSD_n), then the fixed-order mean over n -> loss.
+ * Backward: one workgroup per (image, 16x32 tile of pooled pixels = 32x64 pixels of sr) recomputes the pooled luma on a 2-position
+ * halo and a, b, GMS on a 1-position halo, d loss / d GMS = (d - mean_n) / (Hd Wd GMSD_n N) from `stats`, through d GMS / d a, the
+ * transposed taps, the 1/4 of the pool, the luma coefficient and the clamp's mask (zero where sr lies outside [0, 1]), times *gout
+ * (device scalar: no host sync; applied once, last, so grad is linear in it to the last bit).  Every element of grad is written.  Where grad x = 0 the square root's derivative is taken as 0,
+ * and an image with GMSD_n = 0 gets a zero gradient.  hr gets no gradient and is not range-checked.  NCHW fp32,
+ * N * (tiles per image) < 2^31. ------------------------------------------------------------------------------------------------ */
+typedef struct srk_gmsd_args {
+  const float* sr;                        /* test image [N][C][H][W] (forward, backward; clamped on load)                    */
+  const float* hr;                        /* reference image [N][C][H][W] (forward, backward)                                */
+  int N, C, H, W;
+  double* partial;                        /* [srk_gmsd_tiles(N, C, H, W)][2]: per forward tile (sum d, sum d^2), d = GMS - 1 */
+  float* stats;                           /* [N][2]: finalize writes (mean of d, GMSD_n), backward reads                     */
+  float* loss;                            /* finalize: device scalar, the mean of GMSD_n                                     */
+  const float* gout;                      /* backward: device scalar                                                         */
+  float* grad;                            /* backward: [N][C][H][W] d loss / d sr                                            */
+} srk_gmsd_args;
+/* forward tiles over the whole batch (N images x tiles per image), or -1 when the sizes are refused */
+int srk_gmsd_tiles(int N, int C, int H, int W);
+int srk_gmsd_fwd(const srk_gmsd_args* a, srk_stream_t stream);
+int srk_gmsd_finalize(const srk_gmsd_args* a, srk_stream_t stream);
+int srk_gmsd_bwd(const srk_gmsd_args* a, srk_stream_t stream);
+
 /* ---- SSIM with piq.ssim's defaults (reference srmodel.py:52-53,567-593 -> piq.ssim): images are average-pooled by
  * `pool` = max(1, round(min(H, W) / 256)) (floor division of the extent, as F.avg_pool2d), filtered with the separable
  * 11-tap Gaussian (sigma), and the SSIM map of the VALID region ((Hp-10) x (Wp-10)) is summed per (image, channel)

@@ -229,6 +229,11 @@ class SsimLossArgs(C.Structure):
                 ("grad", _p)]
 
 
+class GmsdArgs(C.Structure):
+    _fields_ = [("sr", _p), ("hr", _p), ("N", _i), ("C", _i), ("H", _i), ("W", _i), ("partial", _p), ("stats", _p), ("loss", _p),
+                ("gout", _p), ("grad", _p)]
+
+
 class MsSsimLossArgs(C.Structure):
     _fields_ = [("sr", _p), ("hr", _p), ("N", _i), ("C", _i), ("H", _i), ("W", _i), ("workspace", _p), ("partials", _p), ("table", _p),
                 ("loss", _p), ("gout", _p), ("gwork", _p), ("grad", _p)]
@@ -315,6 +320,9 @@ LAUNCHERS = {
     "srk_ms_ssim_loss_fwd": MsSsimLossArgs,
     "srk_ms_ssim_loss_finalize": MsSsimLossArgs,
     "srk_ms_ssim_loss_bwd": MsSsimLossArgs,
+    "srk_gmsd_fwd": GmsdArgs,
+    "srk_gmsd_finalize": GmsdArgs,
+    "srk_gmsd_bwd": GmsdArgs,
     "srk_unfold_nhwc": UnfoldNhwcArgs,
     "srk_fold_nhwc": FoldNhwcArgs,
     "srk_chan_stats": ChanStatsArgs,
@@ -341,7 +349,7 @@ OTHER_SYMBOLS = ("srk_conv_tile", "srk_last_error", "srk_version", "srk_device_c
                  "srk_rmsprop_step_scaled", "srk_rmsprop_check_scaled", "srk_rmsprop_update_scaled",
                  "srk_conv_trunk", "srk_conv_trunk_ok", "srk_flip_blocks", "srk_flip_mean",
                  "srk_ms_ssim_workspace_bytes", "srk_ms_ssim_tiles", "srk_haarpsi_tiles", "srk_ssim_loss_tiles",
-                 "srk_ms_ssim_loss_workspace_bytes", "srk_ms_ssim_loss_tiles")
+                 "srk_ms_ssim_loss_workspace_bytes", "srk_ms_ssim_loss_tiles", "srk_gmsd_tiles")
 
 _lib = None
 
@@ -442,6 +450,9 @@ def load():
         lib.srk_ms_ssim_loss_workspace_bytes.restype = C.c_longlong
         lib.srk_ms_ssim_loss_tiles.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
         lib.srk_ms_ssim_loss_tiles.restype = C.c_int
+    if not isinstance(getattr(lib, "srk_gmsd_tiles", None), _Absent):
+        lib.srk_gmsd_tiles.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+        lib.srk_gmsd_tiles.restype = C.c_int
     lib.srk_pw_shape_ok.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.srk_pw_shape_ok.restype = C.c_int
     lib.srk_pw_pack_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]

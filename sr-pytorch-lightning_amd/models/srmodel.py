@@ -96,8 +96,16 @@ def _ms_ssim_loss(sr, hr):
     return ms_ssim_loss.ms_ssim_loss(sr, hr)
 
 
+def _gmsd_loss(sr, hr):
+    """piq.GMSDLoss (gradient magnitude similarity deviation), called like the other piq losses on clamp(sr, 0, 1) and hr: the
+    deviation itself, 0 for a perfect match; the edge-aware term that, unlike the reference's `edge_loss`, carries a gradient.  On the
+    GPU the fused HIP forward/backward (gmsd.GMSDLossFn, which clamps inside), elsewhere gmsd.gmsd_torch.  1 or 3 channels."""
+    from .. import gmsd
+    return gmsd.gmsd_loss(sr, hr)
+
+
 _supported_losses = {"l1": _l1_loss, "l2": F.mse_loss, "mae": _l1_loss, "mse": F.mse_loss, "flip": _flip_loss,
-                     "haarpsi": _haarpsi_loss, "ssim": _ssim_loss, "ms_ssim": _ms_ssim_loss}
+                     "haarpsi": _haarpsi_loss, "ssim": _ssim_loss, "ms_ssim": _ms_ssim_loss, "gmsd": _gmsd_loss}
 _MS_SSIM_MIN_PATCH = 161          # ops_metrics.MS_SSIM_MIN_SIZE: (11 - 1) * 2^4 + 1
 _out_of_scope_losses = {"adaptive", "dists", "edge_loss", "lpips", "pencil_sketch", "pieapp"}
 
@@ -209,8 +217,14 @@ def _flip_metric(x, y):
     return flip.flip(x, y)
 
 
+def _gmsd_metric(x, y):
+    """GMSD (piq.GMSDLoss's value): the deviation of x against y, no gradient, lower is better; HIP forward launches on the GPU."""
+    from .. import gmsd
+    return gmsd.gmsd(x, y)
+
+
 _supported_metrics = {"PSNR": _psnr, "SSIM": _ssim, "PSNR-Y": _psnr_y_metric, "FLIP": _flip_metric,   # srmodel.py:47-54 (+ PSNR-Y)
-                      "MS-SSIM": _ms_ssim}
+                      "MS-SSIM": _ms_ssim, "GMSD": _gmsd_metric}
 
 
 def _dtype_from_precision(precision):

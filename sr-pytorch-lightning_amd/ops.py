@@ -1510,3 +1510,4 @@ from .flip import *          # noqa: E402,F401,F403  FLIP loss and metric (csrc/
 from .haarpsi import *       # noqa: E402,F401,F403  HaarPSI loss (csrc/haarpsi.hip)
 from .ssim_loss import *     # noqa: E402,F401,F403  SSIM loss (csrc/ssim_loss.hip)
 from .ms_ssim_loss import *  # noqa: E402,F401,F403  MS-SSIM loss (csrc/ms_ssim_loss.hip)
+from .gmsd import *          # noqa: E402,F401,F403  GMSD loss and metric (csrc/gmsd.hip)

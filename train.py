@@ -28,8 +28,8 @@ def parse(argv=None):
     p.add_argument("--patch_size", type=int, default=128, help="HR patch edge (LR = patch_size // scale_factor)")
     p.add_argument("--batch_size", type=int, default=16)
     p.add_argument("--precision", default="bf16", help="32, 16 or bf16 (Trainer key of the reference)")
-    p.add_argument("--losses", default="l1", help="loss or weighted composite, e.g. l1, \"0.9*l1+0.1*flip\", \"0.9*l1+0.1*haarpsi\", \"0.16*l1+0.84*ssim\", \"0.16*l1+0.84*ms_ssim\" (--patch_size >= 161)")
-    p.add_argument("--metrics", nargs="+", default=None, help="validation metrics (default: the model's, PSNR SSIM); e.g. PSNR SSIM MS-SSIM FLIP")
+    p.add_argument("--losses", default="l1", help="loss or weighted composite, e.g. l1, \"0.9*l1+0.1*flip\", \"0.9*l1+0.1*haarpsi\", \"0.16*l1+0.84*ssim\", \"0.16*l1+0.84*ms_ssim\" (--patch_size >= 161), \"0.9*l1+0.1*gmsd\"")
+    p.add_argument("--metrics", nargs="+", default=None, help="validation metrics (default: the model's, PSNR SSIM); e.g. PSNR SSIM MS-SSIM FLIP GMSD")
     p.add_argument("--optimizer", default="ADAM")
     p.add_argument("--max_steps", type=int, default=100)
     p.add_argument("--max_epochs", type=int, default=-1)
