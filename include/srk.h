@@ -979,6 +979,27 @@ int srk_rmsprop_step_scaled(const srk_rmsprop_args* a, float* scaler_state, srk_
 int srk_rmsprop_check_scaled(const srk_rmsprop_args* a, float* scaler_state, srk_stream_t stream);
 int srk_rmsprop_update_scaled(const srk_rmsprop_args* a, const float* scaler_state, srk_stream_t stream);
 
+/* ---- exponential moving average of the weights (ema.py), csrc/ema.hip ----------------------------------------------------------
+ * One launch over the optimizers' table: srk_adam_slot (`p` the parameter, `g` unused and NULL, `state_off` the tensor's offset in
+ * floats into the flat fp32 `shadow` buffer, `step_idx` unused) and srk_adam_block (one tensor per block).  `op`:
+ *     SRK_EMA_UPDATE : s = s + w * (p - s),  w = weight[0];  count[0] += 1 (one thread, an ordinary store)
+ *     SRK_EMA_SWAP   : p and s exchanged element by element (two swaps restore every bit)
+ *     SRK_EMA_STORE  : s = p            SRK_EMA_LOAD : p = s
+ * `weight` is ONE DEVICE float, w = (float)(1.0 - decay) formed in double by the host, and `count` ONE DEVICE 64-bit integer: both are
+ * read when the launch RUNS, so a replayed hipGraph counts its updates and follows a decay written between two replays.  UPDATE is
+ * at::lerp's form for w < 0.5 (torch.optim.swa_utils.get_ema_multi_avg_fn) used for EVERY w: fp32, three roundings, not contracted.
+ * One exception: w == 1 (decay 0) stores p itself -- the formula's exact value, which fp32's s + (p - s) can miss by an ulp.
+ * `weight` and `count` may be NULL for the other three operations.  Traffic: 12 B per parameter (UPDATE), 16 B (SWAP), 8 B. */
+enum { SRK_EMA_UPDATE = 0, SRK_EMA_SWAP = 1, SRK_EMA_STORE = 2, SRK_EMA_LOAD = 3 };
+typedef struct {
+  const srk_adam_slot* slots; const srk_adam_block* blocks; int nslots, nblocks;
+  float* shadow;
+  const float* weight;
+  long long* count;
+  int op;
+} srk_ema_args;
+int srk_ema_step(const srk_ema_args* a, srk_stream_t stream);
+
 /* ---- tiled and self-ensemble inference (tiling.py), csrc/tile.hip -------------------------------------------------------------
  * The two data movements around the model's forward when a large image is predicted as a batch of overlapping tiles and / or as the
  * mean over the 8 flips and transposes of the input.  Transform id k: bit 0 reverses W, bit 1 reverses H, bit 2 transposes H and W

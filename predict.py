@@ -25,6 +25,8 @@ def main(argv=None):
     p.add_argument("-m", "--model", default="srcnn")
     p.add_argument("-s", "--scale_factor", type=int, default=4)
     p.add_argument("--checkpoint", default="", help="state_dict (.pt / Lightning .ckpt)")
+    p.add_argument("--weights", default="auto", choices=("auto", "ema", "live"),
+                   help="which weights of the checkpoint: the averaged ones ('state_dict_ema', train.py --ema_decay), the live ones, or auto: the averaged ones if the file has them")
     p.add_argument("--precision", default="bf16")
     p.add_argument("--accelerator", default="auto", choices=("auto", "gpu", "cpu"))
     p.add_argument("--default_root_dir", default="results")
@@ -46,7 +48,10 @@ def main(argv=None):
     model = cls(scale_factor=a.scale_factor, precision=a.precision, default_root_dir=a.default_root_dir, predict_datasets=ds_names, **kw)
     if a.checkpoint:
         sd = torch.load(a.checkpoint, map_location="cpu")
-        model.load_state_dict(sd.get("state_dict", sd), strict=True)
+        if a.weights == "ema" and "state_dict_ema" not in sd:
+            raise SystemExit(f"--weights ema: {a.checkpoint} has no 'state_dict_ema'")
+        key = "state_dict_ema" if a.weights != "live" and "state_dict_ema" in sd else "state_dict"
+        model.load_state_dict(sd.get(key, sd), strict=True)
     use_gpu = a.accelerator == "gpu" or (a.accelerator == "auto" and torch.cuda.is_available() and cls is not sr_amd.SRCNN)
     dev = torch.device("cuda" if use_gpu else "cpu")
     model = model.to(dev).eval()

@@ -125,6 +125,13 @@ class RmspropArgs(C.Structure):
                 ("centered", _i), ("maximize", _i)]
 
 
+EMA_UPDATE, EMA_SWAP, EMA_STORE, EMA_LOAD = 0, 1, 2, 3
+
+
+class EmaArgs(C.Structure):
+    _fields_ = [("slots", _p), ("blocks", _p), ("nslots", _i), ("nblocks", _i), ("shadow", _p), ("weight", _p), ("count", _p), ("op", _i)]
+
+
 class WgradArgs(C.Structure):
     _fields_ = [("x", _p), ("x_pitch", _i), ("x_coff", _i), ("x_ps", _i),
                 ("dy", _p), ("dy_pitch", _i), ("dy_coff", _i), ("dy_ps", _i),
@@ -294,6 +301,7 @@ LAUNCHERS = {
     "srk_ranger_step": RangerArgs,
     "srk_sgd_step": SgdArgs,
     "srk_rmsprop_step": RmspropArgs,
+    "srk_ema_step": EmaArgs,
     "srk_chan_finalize": ChanFinalizeArgs,
     "srk_conv2d_wgrad": WgradArgs,
     "srk_wgrad_finalize": WgradFinArgs,

@@ -10,6 +10,7 @@ otherwise from `nn.Module` with no-op logging hooks and `trainer.py`'s own fit l
 Out of scope: perceptual / adaptive losses, Comet /
 TensorBoard image dumps, model-parallel flags (accepted and ignored with a warning).
 """
+import contextlib
 import itertools
 import logging
 from dataclasses import dataclass
@@ -19,6 +20,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .. import ema as _ema
 from .. import optim as _hip_optim
 from .. import tiling as _tiling
 
@@ -267,6 +269,7 @@ class SRModel(_Base):
                  tile_pad: int = _tiling.DEFAULT_TILE_PAD,
                  tile_batch: int = _tiling.DEFAULT_TILE_BATCH,
                  self_ensemble: bool = False,
+                 ema_decay: float = 0.0,
                  **kwargs: dict[str, Any]):
         super().__init__()
         self._logger = logging.getLogger(__name__)
@@ -300,6 +303,10 @@ class SRModel(_Base):
         #: tile carries beyond what it owns, `tile_batch` how many tiles one forward takes; both off is the whole-image path
         _tiling.check_args(tile, tile_pad, tile_batch)
         self._tile, self._tile_pad, self._tile_batch, self._self_ensemble = tile, tile_pad, tile_batch, bool(self_ensemble)
+        #: decay of the exponential moving average of the weights (ema.ParamEMA); 0: off, nothing is allocated and `ema` stays None.
+        #: `Trainer.fit` creates the average and updates it behind every optimizer step; `ema_weights()` evaluates under it
+        _ema.ParamEMA._check_decay(ema_decay)
+        self.ema_decay = float(ema_decay)
         #: arithmetic type of the HIP path: storage dtype of activations / packed weights (fp32 accumulate)
         self.compute_dtype = _dtype_from_precision(precision)
         #: storage dtype of the validation / predict forward.  bf16 keeps 8 mantissa bits on the residual trunk, which
@@ -309,6 +316,22 @@ class SRModel(_Base):
         ep = kwargs.get("eval_precision")
         self.eval_dtype = _dtype_from_precision(ep) if ep is not None else \
             (torch.float16 if self.compute_dtype == torch.bfloat16 else self.compute_dtype)
+
+    #: the `ema.ParamEMA` of the parameters once `make_ema()` has run.  Not a module buffer: `state_dict()` keeps the reference's layout
+    ema = None
+
+    def make_ema(self, decay=None):
+        """Create the average of every floating-point parameter (`decay`: `ema_decay` unless given).  Its shadows start from the
+        current weights and its device table names their addresses, so call it once the model is on its device and any checkpoint is
+        loaded."""
+        self.ema = _ema.ParamEMA(self.parameters(), self.ema_decay if decay is None else decay)
+        return self.ema
+
+    def ema_weights(self):
+        """Context manager: the model runs on the averaged weights inside the block (`ParamEMA.swapped`: exchanged in place, the live
+        ones are back afterwards); a null context when there is no average.  With a `GraphedStep` that still has an update pending,
+        `flush()` first."""
+        return self.ema.swapped() if self.ema is not None else contextlib.nullcontext()
 
     # -- optimizers: srmodel.py:145-154 ------------------------------------------------------------
     def configure_optimizers(self):
@@ -444,6 +467,7 @@ class SRModel(_Base):
         state = dict(self.__dict__)
         state.pop("_srk_packs", None)
         state.pop("_srk_wn", None)
+        state.pop("ema", None)               # (device table, page-locked staging buffer; a copy of the module starts without an average)
         return state
 
     # -- srmodel.py:435-501 ------------------------------------------------------------------------------

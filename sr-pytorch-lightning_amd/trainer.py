@@ -279,6 +279,31 @@ def _eager_step(model, net, optimizer, gsync, scaler, batch):
     return loss.detach()
 
 
+class EmaAfterStep:
+    """Makes `ema.update()` follow EVERY step of `optimizer`, from one place: a pair of torch's optimizer step hooks.  The hooks run
+    inside `Optimizer.step`'s wrapper, so the update lands wherever the step does -- launch by launch, inside a hipGraph capture (the
+    update is then a node of the graph, behind the step's launches, and every replay repeats it), in `GraphedStep.flush()` /
+    `finish()` and behind `OverlappedGraphStep`'s eager step.  A step the `DeviceGradScaler` skips on the device is still a call of
+    `step()`: the average moves towards the unchanged weights and counts it, like timm's, BasicSR's and torch's averaged models.
+    The CPU form of optim.py's classes calls torch's own (also wrapped) `step` from inside theirs: only the outermost call updates."""
+
+    def __init__(self, optimizer, ema):
+        self.ema, self.depth = ema, 0
+        self.handles = (optimizer.register_step_pre_hook(self._pre), optimizer.register_step_post_hook(self._post))
+
+    def _pre(self, optimizer, args, kwargs):
+        self.depth += 1
+
+    def _post(self, optimizer, args, kwargs):
+        self.depth -= 1
+        if self.depth == 0:
+            self.ema.update()
+
+    def remove(self):
+        for h in self.handles:
+            h.remove()
+
+
 class GraphedStep:
     """The training step as hipGraph replays.
 
@@ -736,6 +761,14 @@ class Trainer:
             from .optim import DeviceGradScaler, _TableStep
             scaler = DeviceGradScaler(self.device) if isinstance(optimizer, _TableStep) else torch.amp.GradScaler("cuda")
         self.scaler = scaler
+        # EMA of the weights (ema.ParamEMA): the model's own if it has one already (restored from a checkpoint), else created here --
+        # after the move to the device and the broadcast, so every rank starts from the same shadows and keeps an identical average
+        ema = getattr(model, "ema", None)
+        if ema is None and getattr(model, "ema_decay", 0.0) > 0:
+            ema = model.make_ema()
+        if ema is not None and ema.device != next(model.parameters()).device:
+            raise RuntimeError(f"the model's EMA lives on {ema.device}, its parameters on {next(model.parameters()).device}: call make_ema() after .to(device)")
+        ema_hook = EmaAfterStep(optimizer, ema) if ema is not None else None
         graphed = None
         if self.use_graph and (scaler is None or hasattr(scaler, "state")) and self.device.type == "cuda" and not use_ddp:
             graphed = GraphedStep(model, net, optimizer, gsync, warm_steps=11 if gsync is not None else 3, scaler=scaler)
@@ -760,6 +793,8 @@ class Trainer:
                 graphed.finish()         # (multi-rank graph form: the last replay's update)
         finally:                 # whatever ended the loop: nothing stays attached to the parameters, the deferral switch is what it was
             self.graphed = graphed
+            if ema_hook is not None:
+                ema_hook.remove()
             for gs in {id(g): g for g in (gsync, getattr(graphed, "gsync", None), getattr(getattr(graphed, "ogs", None), "gsync", None)) if g is not None}.values():
                 gs.detach()
             unwrap_ddp(net)

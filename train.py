@@ -38,7 +38,9 @@ def parse(argv=None):
     p.add_argument("--strategy", default="ddp", help="accepted for compatibility: data parallel is the only strategy")
     p.add_argument("--default_root_dir", default=".")
     p.add_argument("--checkpoint", default=None, help="state_dict (.pt / Lightning .ckpt) to start from")
-    p.add_argument("--save", default=None, help="where rank 0 writes {'state_dict': ...} at the end")
+    p.add_argument("--save", default=None, help="where rank 0 writes {'state_dict': ...} at the end (with --ema_decay also 'state_dict_ema' and 'ema_num_updates')")
+    p.add_argument("--ema_decay", type=float, default=0.0, help="decay of the exponential moving average of the weights, e.g. 0.999 (0: off); "
+                   "validation and 'state_dict_ema' use the averaged weights")
     p.add_argument("--train_dir", default=None, help="directory of HR training images (default: synthetic patches)")
     p.add_argument("--val_dir", default=None, help="directory of HR validation images")
     p.add_argument("--eval_datasets", nargs="+", default=None)
@@ -84,11 +86,17 @@ def main(argv=None):
     elif a.val_dir:
         kw["eval_datasets"] = [os.path.basename(os.path.normpath(a.val_dir))]
     model = cls(scale_factor=a.scale_factor, patch_size=a.patch_size, batch_size=a.batch_size, precision=a.precision,
-                losses=a.losses, optimizer=a.optimizer, default_root_dir=a.default_root_dir, devices=a.devices, **kw)
+                losses=a.losses, optimizer=a.optimizer, default_root_dir=a.default_root_dir, devices=a.devices, ema_decay=a.ema_decay, **kw)
+    sd = None
     if a.checkpoint:
         sd = torch.load(a.checkpoint, map_location="cpu")
         model.load_state_dict(sd.get("state_dict", sd), strict=True)
     tr = T.Trainer(device="cuda" if use_gpu else "cpu", max_steps=a.max_steps, log_every=a.log_every)
+    if a.ema_decay > 0 and sd is not None and "state_dict_ema" in sd:
+        # a checkpoint that carries an average restores it (on the device the weights train on); without one fit() starts the
+        # average from the loaded weights
+        model.to(tr.device)
+        model.make_ema().load_state_dict(model, sd["state_dict_ema"], num_updates=sd.get("ema_num_updates"))
     lr_edge = a.patch_size // a.scale_factor
 
     if a.train_dir:
@@ -119,7 +127,7 @@ def main(argv=None):
         pairs, stems = D.load_image_pairs(a.val_dir, a.scale_factor)
         mine = D.shard_indices(len(pairs), tr.rank, tr.world, shuffle=False)
         model.eval()
-        with torch.no_grad():
+        with torch.no_grad(), model.ema_weights():       # (fit() has flushed: no update is pending)
             for k, i in enumerate(mine):
                 lr, hr = pairs[i]
                 batch = {"lr": D.image_to_tensor(lr)[None].to(tr.device), "hr": D.image_to_tensor(hr)[None].to(tr.device), "path": [stems[i]]}
@@ -134,7 +142,11 @@ def main(argv=None):
             print("validation: " + ", ".join(f"{k} {float(v):.4f}" for k, v in metrics.items()), flush=True)
     if a.save and tr.rank == 0:
         os.makedirs(os.path.dirname(os.path.abspath(a.save)), exist_ok=True)
-        torch.save({"state_dict": model.state_dict()}, a.save)
+        ckpt = {"state_dict": model.state_dict()}
+        if model.ema is not None:
+            ckpt["state_dict_ema"] = model.ema.state_dict(model)
+            ckpt["ema_num_updates"] = model.ema.num_updates
+        torch.save(ckpt, a.save)
     if tr.rank == 0 and tr.losses:
         print(f"done: {len(tr.losses)} steps, last loss {tr.losses[-1]:.6f}", flush=True)
     if torch.distributed.is_available() and torch.distributed.is_initialized():
