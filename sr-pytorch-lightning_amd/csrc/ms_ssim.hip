@@ -1,32 +1,25 @@
-// MS-SSIM with piq.multi_scale_ssim's defaults (reference configs/train_default_sr.yml `metrics`), on the device:
+// MS-SSIM with piq.multi_scale_ssim's defaults (reference configs/train_default_sr.yml `metrics`), on the device (the levels' geometry
+// and `bin` are ssim_core.h's):
 //   ms_pool_kernel     level k of both images from level k-1: replicate-pad p = max(H % 2, W % 2) on the top and left, then a
 //                      2x2 / stride-2 average (F.pad + F.avg_pool2d); one launch per level, levels 1-4 in the caller's workspace
 //   ms_maps_kernel     one launch for all five levels: the block index runs over every level's 16x16 valid-map tiles; each
-//                      workgroup stages its tile + 10-pixel halo of both images in LDS, runs the separable 11-tap Gaussian over
-//                      the five moments of the tile shifted by one of its pixels (otherwise as ssim_kernel in data.hip) and
-//                      writes (sum ss, sum cs) over its tile to a fixed slot
+//                      workgroup stages its tile + 10-pixel halo of both images in LDS, runs the separable 11-tap Gaussian (run-time
+//                      taps and constants) over the five moments of the tile shifted by one of its pixels (otherwise as ssim_kernel
+//                      in data.hip) and writes (sum ss, sum cs) over its tile to a fixed slot
 //   ms_final_kernel    one wave per (image, channel) plane (8 waves): the plane's partials summed per level in a fixed order (lane-strided,
 //                      then a shuffle tree), divided by the valid counts, relu / pow / product, then the mean over all planes
 // No float atomics anywhere: the result is bit-reproducible.  fp32 maps (like piq), double sums.
 #include <math.h>
-#include "srk_common.h"
+#include "ssim_core.h"
 
 namespace {
 
-constexpr int MS_LEVELS = 5;
-constexpr int MS_TILE = 16;
+constexpr int MS_LEVELS = ssim::LEVELS;
+constexpr int MS_TILE = ssim::TILE;
 constexpr int MS_FINAL_THREADS = 512;
 
-struct MsLevel {
-  const float* x;                 // level plane 0 of image x; plane p starts at x + p * H * W
-  const float* y;
-  int H, W;
-  int tilesX;
-  int first;                      // first tile of this level in a plane's tile range
-};
-
 struct MsMapsArgs {
-  MsLevel lv[MS_LEVELS];
+  ssim::Level lv[MS_LEVELS];
   float g[11];                    // normalised Gaussian taps
   float c1, c2;
   int tiles;                      // tiles per plane, all levels
@@ -136,15 +129,6 @@ __global__ __launch_bounds__(256) void ms_maps_kernel(const MsMapsArgs a) {
   }
 }
 
-// Per level, the value the product uses: cs for levels 0-3, ss for the last level.  Adding 0.0 to the other bins leaves them unchanged.
-__device__ __forceinline__ void ms_bin(const MsFinalArgs& a, int t, double2 v, double (&bin)[MS_LEVELS]) {
-#pragma unroll
-  for (int k = 0; k < MS_LEVELS; ++k) {
-    const double val = k < MS_LEVELS - 1 ? v.y : v.x;
-    bin[k] += (t >= a.first[k] && t < a.first[k + 1]) ? val : 0.0;
-  }
-}
-
 __global__ __launch_bounds__(MS_FINAL_THREADS) void ms_final_kernel(const MsFinalArgs a) {
   __shared__ double red[MS_FINAL_THREADS / 64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -160,7 +144,7 @@ __global__ __launch_bounds__(MS_FINAL_THREADS) void ms_final_kernel(const MsFina
 #pragma unroll
       for (int k = 0; k < 8; ++k) v[k] = i + 64 * k < T ? p[i + 64 * k] : make_double2(0.0, 0.0);
 #pragma unroll
-      for (int k = 0; k < 8; ++k) ms_bin(a, i + 64 * k, v[k], bin);
+      for (int k = 0; k < 8; ++k) ssim::bin(a, i + 64 * k, v[k], bin);
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1)
@@ -189,39 +173,23 @@ __global__ __launch_bounds__(MS_FINAL_THREADS) void ms_final_kernel(const MsFina
   }
 }
 
-constexpr int MS_MIN_SIZE = (11 - 1) * (1 << (MS_LEVELS - 1)) + 1;     // 161
-
-// level sizes, as piq builds them
-void ms_level_sizes(int H, int W, int (&h)[MS_LEVELS], int (&w)[MS_LEVELS]) {
-  h[0] = H; w[0] = W;
-  for (int k = 1; k < MS_LEVELS; ++k) {
-    const int p = (h[k - 1] % 2) | (w[k - 1] % 2);
-    h[k] = (h[k - 1] + p) / 2;
-    w[k] = (w[k - 1] + p) / 2;
-  }
-}
-
-int ms_tiles_of(int h, int w) { return ((w - 10 + MS_TILE - 1) / MS_TILE) * ((h - 10 + MS_TILE - 1) / MS_TILE); }
-
 }  // namespace
 
 extern "C" long long srk_ms_ssim_workspace_bytes(int N, int C, int H, int W) {
-  if (N <= 0 || C <= 0 || H < MS_MIN_SIZE || W < MS_MIN_SIZE) return -1;
+  if (N <= 0 || C <= 0 || H < ssim::MIN_SIZE || W < ssim::MIN_SIZE) return -1;
   int h[MS_LEVELS], w[MS_LEVELS];
-  ms_level_sizes(H, W, h, w);
-  long long floats = 0;
-  for (int k = 1; k < MS_LEVELS; ++k) floats += 2LL * N * C * h[k] * w[k];
-  return (floats * 4 + 255) / 256 * 256;
+  ssim::level_sizes(H, W, h, w);
+  return ssim::workspace_bytes((long long)N * C, h, w);
 }
 
 extern "C" int srk_ms_ssim_tiles(int H, int W, int* first) {
-  if (H < MS_MIN_SIZE || W < MS_MIN_SIZE) return -1;
+  if (H < ssim::MIN_SIZE || W < ssim::MIN_SIZE) return -1;
   int h[MS_LEVELS], w[MS_LEVELS];
-  ms_level_sizes(H, W, h, w);
+  ssim::level_sizes(H, W, h, w);
   int t = 0;
   for (int k = 0; k < MS_LEVELS; ++k) {
     if (first) first[k] = t;
-    t += ms_tiles_of(h[k], w[k]);
+    t += ssim::map_tiles(h[k], w[k]);
   }
   if (first) first[MS_LEVELS] = t;
   return t;
@@ -230,34 +198,20 @@ extern "C" int srk_ms_ssim_tiles(int H, int W, int* first) {
 extern "C" int srk_ms_ssim(const srk_ms_ssim_args* a, srk_stream_t stream) {
   SRK_CHECK_ARG(a && a->x && a->y && a->workspace && a->partials && a->out, "srk_ms_ssim: null pointer");
   SRK_CHECK_ARG(a->N > 0 && a->C > 0 && (long long)a->N * a->C <= 65535, "srk_ms_ssim: bad sizes N=%d C=%d", a->N, a->C);
-  SRK_CHECK_ARG(a->H >= MS_MIN_SIZE && a->W >= MS_MIN_SIZE, "srk_ms_ssim: image %dx%d is smaller than %dx%d", a->H, a->W,
-                MS_MIN_SIZE, MS_MIN_SIZE);
+  SRK_CHECK_ARG(a->H >= ssim::MIN_SIZE && a->W >= ssim::MIN_SIZE, "srk_ms_ssim: image %dx%d is smaller than %dx%d", a->H, a->W,
+                ssim::MIN_SIZE, ssim::MIN_SIZE);
   SRK_CHECK_ARG(a->sigma > 0.f, "srk_ms_ssim: sigma must be positive");
   SRK_CHECK_ARG((uintptr_t)a->partials % 16 == 0 && (uintptr_t)a->workspace % 4 == 0, "srk_ms_ssim: workspace alignment");
   const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int planes = a->N * a->C;
   int h[MS_LEVELS], w[MS_LEVELS];
-  ms_level_sizes(a->H, a->W, h, w);
+  ssim::level_sizes(a->H, a->W, h, w);
   MsMapsArgs m;
   MsFinalArgs f;
-  m.lv[0].x = a->x;
-  m.lv[0].y = a->y;
-  float* ws = a->workspace;
-  int t = 0;
+  const int t = ssim::layout_levels(a->x, a->y, a->workspace, planes, h, w, m.lv);
   for (int k = 0; k < MS_LEVELS; ++k) {
-    if (k > 0) {
-      const size_t n = (size_t)planes * h[k] * w[k];
-      m.lv[k].x = ws;
-      m.lv[k].y = ws + n;
-      ws += 2 * n;
-    }
-    m.lv[k].H = h[k];
-    m.lv[k].W = w[k];
-    m.lv[k].tilesX = (w[k] - 10 + MS_TILE - 1) / MS_TILE;
-    m.lv[k].first = t;
-    f.first[k] = t;
-    f.count[k] = (float)((h[k] - 10) * (w[k] - 10));
-    t += ms_tiles_of(h[k], w[k]);
+    f.first[k] = m.lv[k].first;
+    f.count[k] = (float)((h[k] - ssim::HALO) * (w[k] - ssim::HALO));
   }
   f.first[MS_LEVELS] = t;
   double g[11], gs = 0.0;
@@ -278,7 +232,7 @@ extern "C" int srk_ms_ssim(const srk_ms_ssim_args* a, srk_stream_t stream) {
   f.out = a->out;
 
   for (int k = 1; k < MS_LEVELS; ++k) {
-    const int p = (h[k - 1] % 2) | (w[k - 1] % 2);
+    const int p = ssim::level_pad(h[k - 1], w[k - 1]);
     hipLaunchKernelGGL(ms_pool_kernel, dim3((unsigned)((h[k] * w[k] + 255) / 256), (unsigned)planes), dim3(256), 0, s,
                        m.lv[k - 1].x, m.lv[k - 1].y, h[k - 1], w[k - 1], const_cast<float*>(m.lv[k].x), const_cast<float*>(m.lv[k].y),
                        h[k], w[k], p);

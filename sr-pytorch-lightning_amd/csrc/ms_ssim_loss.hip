@@ -1,12 +1,12 @@
 // MS-SSIM loss, 1 - MS-SSIM(clamp(sr, 0, 1), hr) with piq.multi_scale_ssim's defaults (piq.MultiScaleSSIMLoss; the metric twin is
-// ms_ssim.hip, the single-scale loss ssim_loss.hip): include/srk.h "MS-SSIM loss", sr_amd/ms_ssim_loss.py.  One (image, channel)
-// plane at a time; level 0 is (clamp(sr), hr), level k > 0 is level k-1 replicate-padded by p = max(H % 2, W % 2) on the top and
-// left and averaged 2x2 / stride 2.
+// ms_ssim.hip, the single-scale loss ssim_loss.hip): include/srk.h "MS-SSIM loss", sr_amd/ms_ssim_loss.py.  The constants, the moment
+// passes, the map values and the levels' geometry are ssim_core.h's.  One (image, channel) plane at a time; level 0 is
+// (clamp(sr), hr), level k > 0 is level k-1 replicate-padded by p = max(H % 2, W % 2) on the top and left and averaged 2x2 / stride 2.
 //   ml_pool_kernel      level k of both images from level k-1 (ms_pool_kernel's arithmetic); the clamp of sr is folded into the reads
 //                       of level 0, so no clamped copy of the image exists; one launch per level, levels 1-4 in the caller's workspace
 //   ml_maps_kernel      one launch for all five levels: one workgroup per (plane, 16x16 tile of a level's valid map) stages the tile +
-//                       10-pixel halo of both images in LDS (level 0: sr clamped on load), runs the separable 11-tap Gaussian over the
-//                       five moments and writes (sum ss, sum cs) over its tile to a fixed slot
+//                       10-pixel halo of both images in LDS (level 0: sr clamped on load) and writes (sum ss, sum cs) over its tile
+//                       to a fixed slot
 //   ml_final_kernel     one workgroup, one wave per plane at a time: the plane's partials summed per level in a fixed order, the level
 //                       means m_k (cs for k < 4, ss for k = 4), v = prod m_k^w_k (0 if any m_k <= 0), loss = 1 - mean v, and the
 //                       table[plane][k] = w_k v / (m_k count_k planes) the backward scales by (all 0 for a plane with any m_k <= 0:
@@ -19,40 +19,23 @@
 //                       column the pooling's floor drops; twice the share on row / column 0 when p = 1: the replicated pad) and
 //                       writes level k's gradient once.  Level 0 multiplies the sum by *gout, applies the clamp's mask and writes grad.
 // No atomics anywhere and fixed-order sums: bit-reproducible.  (plane, tile) share blockIdx.x in every launch.  fp32 maps (like piq),
-// double sums.  Both images are held and filtered as x - 1/2, y - 1/2 (ssim_loss.hip: SL_SHIFT).  The backward is bound, like the
-// SSIM loss's, by LDS reads of the 11-tap passes (one dword per multiply-add), not by HBM.
-// Plain fp32 VALU (no MFMA: 11-tap separable filters).  The library builds with -ffp-contract=off.
+// double sums.  The backward is bound, like the SSIM loss's, by LDS reads of the 11-tap passes (one dword per multiply-add), not by HBM.
 #include <math.h>
-#include "srk_common.h"
+#include "ssim_core.h"
 
 namespace {
 
-constexpr int ML_LEVELS = 5;
+using ssim::HALO;
+constexpr int ML_LEVELS = ssim::LEVELS;
 constexpr int ML_THREADS = 256;
-constexpr int ML_K = 11, ML_HALO = ML_K - 1;
-constexpr int ML_FT = 16;                              // forward tile edge, map positions
+constexpr int ML_FT = ssim::TILE;                      // forward tile edge, map positions
 constexpr int ML_BTY = 16, ML_BTX = 32;                // backward tile, pixels of the level
 constexpr int ML_FIN_THREADS = 512;
-constexpr int ML_MIN_SIZE = ML_HALO * (1 << (ML_LEVELS - 1)) + 1;      // 161
-constexpr float ML_C1 = 1e-4f, ML_C2 = 9e-4f;          // (0.01)^2, (0.03)^2: data range 1
-constexpr float ML_SHIFT = 0.5f;
 static_assert(ML_FT * ML_FT == ML_THREADS, "maps: one thread per map position");
-// exp(-(k - 5)^2 / (2 * 1.5^2)) / sum, rounded from float64
-__device__ __constant__ float kMlG[ML_K] = {0.001028380123898387f, 0.0075987582094967365f, 0.036000773310661316f, 0.10936068743467331f,
-                                            0.21300554275512695f,  0.26601171493530273f,   0.21300554275512695f,  0.10936068743467331f,
-                                            0.036000773310661316f, 0.0075987582094967365f, 0.001028380123898387f};
 const double kMlWeight[ML_LEVELS] = {0.0448, 0.2856, 0.3001, 0.2363, 0.1333};      // piq.multi_scale_ssim's scale_weights
 
-struct MlLevel {
-  const float* x;                 // plane 0 of the level of image x (level 0: sr itself); plane q starts at x + q * H * W
-  const float* y;
-  int H, W;
-  int tilesX;
-  int first;                      // first map tile of this level in a plane's tile range
-};
-
 struct MlMapsArgs {
-  MlLevel lv[ML_LEVELS];
+  ssim::Level lv[ML_LEVELS];
   int tiles;                      // map tiles per plane, all levels
   double* partials;               // [planes][tiles][2]: (sum ss, sum cs)
 };
@@ -116,46 +99,16 @@ SRK_DEV void ml_load_region(const float* xs, const float* ys, int H, int W, int 
       const size_t o = (size_t)py * W + px;
       vx = xs[o];
       if (clampx) vx = fminf(fmaxf(vx, 0.f), 1.f);
-      vx -= ML_SHIFT;
-      vy = ys[o] - ML_SHIFT;
+      vx -= ssim::SHIFT;
+      vy = ys[o] - ssim::SHIFT;
     }
     X[r][c] = vx;
     Y[r][c] = vy;
   }
 }
 
-// horizontal pass: Hm[q][r][c] = sum_k G[k] * moment_q(r, c + k) for the RY rows and the RX - 10 columns
-template <int RY, int RX>
-SRK_DEV void ml_moments_rows(const float (*X)[RX + 1], const float (*Y)[RX + 1], float (*Hm)[RY][RX - ML_HALO]) {
-  constexpr int SX = RX - ML_HALO;
-  for (int i = threadIdx.x; i < RY * SX; i += ML_THREADS) {
-    const int r = i / SX, c = i - r * SX;
-    float m[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int k = 0; k < ML_K; ++k) {
-      const float xv = X[r][c + k], yv = Y[r][c + k], w = kMlG[k];
-      m[0] += w * xv; m[1] += w * yv; m[2] += w * (xv * xv); m[3] += w * (yv * yv); m[4] += w * (xv * yv);
-    }
-#pragma unroll
-    for (int q = 0; q < 5; ++q) Hm[q][r][c] = m[q];
-  }
-}
-
-// vertical pass at map position (r, c) of the tile: G*x', G*y', G*x'x', G*y'y', G*x'y'
-template <int RY, int SX>
-SRK_DEV void ml_moments_at(const float (*Hm)[RY][SX], int r, int c, float m[5]) {
-#pragma unroll
-  for (int q = 0; q < 5; ++q) m[q] = 0.f;
-#pragma unroll
-  for (int k = 0; k < ML_K; ++k) {
-    const float w = kMlG[k];
-#pragma unroll
-    for (int q = 0; q < 5; ++q) m[q] += w * Hm[q][r + k][c];
-  }
-}
-
 __global__ __launch_bounds__(ML_THREADS) void ml_maps_kernel(const MlMapsArgs a) {
-  constexpr int R = ML_FT + ML_HALO;
+  constexpr int R = ML_FT + HALO;
   __shared__ float X[R][R + 1], Y[R][R + 1];
   __shared__ float Hm[5][R][ML_FT];
   __shared__ double red[ML_THREADS / 64][2];
@@ -173,19 +126,18 @@ __global__ __launch_bounds__(ML_THREADS) void ml_maps_kernel(const MlMapsArgs a)
   const size_t po = (size_t)plane * H * W;
   ml_load_region<R, R>(xs + po, ys + po, H, W, y0, x0, level0, X, Y);
   __syncthreads();
-  ml_moments_rows<R, R>(X, Y, Hm);
+  ssim::moments_rows<ML_THREADS, R, R>(X, Y, Hm);
   __syncthreads();
   const int r = tid / ML_FT, c = tid % ML_FT;
-  double ss_acc = 0.0, cs_acc = 0.0;
-  if (y0 + r + ML_HALO < H && x0 + c + ML_HALO < W) {
+  // cs before ss: declared the other way round the two sums swap registers behind map_values; the order is kept so the kernel's
+  // instructions stay as they were
+  double cs_acc = 0.0, ss_acc = 0.0;
+  if (y0 + r + HALO < H && x0 + c + HALO < W) {
     float m[5];
-    ml_moments_at<R, ML_FT>(Hm, r, c, m);
-    const float sxx = m[2] - m[0] * m[0], syy = m[3] - m[1] * m[1], sxy = m[4] - m[0] * m[1];
-    const float mx = m[0] + ML_SHIFT, my = m[1] + ML_SHIFT;
-    const float cs = (2.f * sxy + ML_C2) / (sxx + syy + ML_C2);
-    const float ss = (2.f * mx * my + ML_C1) / (mx * mx + my * my + ML_C1) * cs;
-    ss_acc = (double)ss;
-    cs_acc = (double)cs;
+    ssim::moments_at<R, ML_FT>(Hm, r, c, m);
+    const ssim::MapValues v = ssim::map_values(m);
+    ss_acc = (double)v.ss;
+    cs_acc = (double)v.cs;
   }
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
@@ -199,15 +151,6 @@ __global__ __launch_bounds__(ML_THREADS) void ml_maps_kernel(const MlMapsArgs a)
     v.x = ((red[0][0] + red[1][0]) + red[2][0]) + red[3][0];
     v.y = ((red[0][1] + red[1][1]) + red[2][1]) + red[3][1];
     reinterpret_cast<double2*>(a.partials)[blockIdx.x] = v;
-  }
-}
-
-// Per level, the value the product uses: cs for levels 0-3, ss for the last level.  Adding 0.0 to the other bins leaves them unchanged.
-__device__ __forceinline__ void ml_bin(const MlFinalArgs& a, int t, double2 v, double (&bin)[ML_LEVELS]) {
-#pragma unroll
-  for (int k = 0; k < ML_LEVELS; ++k) {
-    const double val = k < ML_LEVELS - 1 ? v.y : v.x;
-    bin[k] += (t >= a.first[k] && t < a.first[k + 1]) ? val : 0.0;
   }
 }
 
@@ -226,7 +169,7 @@ __global__ __launch_bounds__(ML_FIN_THREADS) void ml_final_kernel(const MlFinalA
 #pragma unroll
       for (int k = 0; k < 8; ++k) v[k] = i + 64 * k < T ? p[i + 64 * k] : make_double2(0.0, 0.0);
 #pragma unroll
-      for (int k = 0; k < 8; ++k) ml_bin(a, i + 64 * k, v[k], bin);
+      for (int k = 0; k < 8; ++k) ssim::bin(a, i + 64 * k, v[k], bin);
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1)
@@ -266,8 +209,8 @@ __global__ __launch_bounds__(ML_FIN_THREADS) void ml_final_kernel(const MlFinalA
 // SS: the adjoint of the SSIM map (last level); otherwise of the contrast-structure map
 template <bool SS>
 __global__ __launch_bounds__(ML_THREADS) void ml_bwd_kernel(const MlBwdArgs a) {
-  constexpr int SY = ML_BTY + ML_HALO, SX = ML_BTX + ML_HALO;    // map positions whose windows touch the tile
-  constexpr int RY = SY + ML_HALO, RX = SX + ML_HALO;            // pixels those positions read
+  constexpr int SY = ML_BTY + HALO, SX = ML_BTX + HALO;          // map positions whose windows touch the tile
+  constexpr int RY = SY + HALO, RX = SX + HALO;                  // pixels those positions read
   __shared__ float X[RY][RX + 1], Y[RY][RX + 1];
   __shared__ float Hm[5][RY][SX];
   __shared__ float adj[3][SY][SX + 1];                           // m, a, b of the map positions (0 where not valid)
@@ -279,25 +222,25 @@ __global__ __launch_bounds__(ML_THREADS) void ml_bwd_kernel(const MlBwdArgs a) {
   const int H = a.H, W = a.W;
   const size_t po = (size_t)plane * H * W;
   // region pixel (r, c) is pixel (i0 - 10 + r, j0 - 10 + c); map position (r, c) of the tile is (i0 - 10 + r, j0 - 10 + c) too
-  ml_load_region<RY, RX>(a.x + po, a.y + po, H, W, i0 - ML_HALO, j0 - ML_HALO, a.level0, X, Y);
+  ml_load_region<RY, RX>(a.x + po, a.y + po, H, W, i0 - HALO, j0 - HALO, a.level0, X, Y);
   __syncthreads();
-  ml_moments_rows<RY, RX>(X, Y, Hm);
+  ssim::moments_rows<ML_THREADS, RY, RX>(X, Y, Hm);
   __syncthreads();
   for (int i = tid; i < SY * SX; i += ML_THREADS) {
     const int r = i / SX, c = i - r * SX;
-    const int pi = i0 - ML_HALO + r, pj = j0 - ML_HALO + c;
+    const int pi = i0 - HALO + r, pj = j0 - HALO + c;
     float gm = 0.f, ga = 0.f, gb = 0.f;
-    if (pi >= 0 && pi + ML_HALO < H && pj >= 0 && pj + ML_HALO < W) {
+    if (pi >= 0 && pi + HALO < H && pj >= 0 && pj + HALO < W) {
       float m[5];
-      ml_moments_at<RY, SX>(Hm, r, c, m);
+      ssim::moments_at<RY, SX>(Hm, r, c, m);
       const float ux = m[0], uy = m[1];                          // the shifted means: what s_xx, s_xy see
       const float sxx = m[2] - ux * ux, syy = m[3] - uy * uy, sxy = m[4] - ux * uy;
-      const float ib2 = 1.f / (sxx + syy + ML_C2);
-      const float cs = (2.f * sxy + ML_C2) * ib2;
+      const float ib2 = 1.f / (sxx + syy + ssim::C2);
+      const float cs = (2.f * sxy + ssim::C2) * ib2;
       if (SS) {
-        const float mx = ux + ML_SHIFT, my = uy + ML_SHIFT;
-        const float ib1 = 1.f / (mx * mx + my * my + ML_C1);
-        const float l = (2.f * mx * my + ML_C1) * ib1;           // S = l * cs
+        const float mx = ux + ssim::SHIFT, my = uy + ssim::SHIFT;
+        const float ib1 = 1.f / (mx * mx + my * my + ssim::C1);
+        const float l = (2.f * mx * my + ssim::C1) * ib1;        // S = l * cs
         ga = -(l * cs) * ib2;                                    // through sigma_xx
         gb = 2.f * l * ib2;                                      // through sigma_xy
         // d S / d (G*x') in full: 2 mu_y cs / B1 - 2 mu_x S / B1 - u_y b - 2 u_x a, grouped so that each difference is taken once
@@ -318,8 +261,8 @@ __global__ __launch_bounds__(ML_THREADS) void ml_bwd_kernel(const MlBwdArgs a) {
     const int r = i / ML_BTX, c = i - r * ML_BTX;
     float v[3] = {0.f, 0.f, 0.f};
 #pragma unroll
-    for (int k = 0; k < ML_K; ++k) {
-      const float w = kMlG[k];
+    for (int k = 0; k < ssim::K; ++k) {
+      const float w = ssim::kG[k];
 #pragma unroll
       for (int q = 0; q < 3; ++q) v[q] += w * adj[q][r][c + k];
     }
@@ -342,12 +285,12 @@ __global__ __launch_bounds__(ML_THREADS) void ml_bwd_kernel(const MlBwdArgs a) {
     if (pi >= H || pj >= W) continue;
     float v[3] = {0.f, 0.f, 0.f};
 #pragma unroll
-    for (int k = 0; k < ML_K; ++k) {
-      const float w = kMlG[k];
+    for (int k = 0; k < ssim::K; ++k) {
+      const float w = ssim::kG[k];
 #pragma unroll
       for (int q = 0; q < 3; ++q) v[q] += w * Ha[q][r + k][c];
     }
-    const float x = X[r + ML_HALO][c + ML_HALO], y = Y[r + ML_HALO][c + ML_HALO];      // x', y': the shifted pixels
+    const float x = X[r + HALO][c + HALO], y = Y[r + HALO][c + HALO];            // x', y': the shifted pixels
     float g = tk != 0.f ? (v[0] + 2.f * x * v[1] + y * v[2]) * gs : 0.f;
     if (gp) {
       // padded row pi + p lies in parent row (pi + p) / 2; with p = 1 the replicated padded row 0 is source row 0 as well and
@@ -378,21 +321,16 @@ struct MlGeom {
 
 // level sizes as piq builds them, the tilings of every launch, and the refusals: 0, or -1 when the kernels cannot run the sizes
 static int ml_geometry(int N, int C, int H, int W, MlGeom* g) {
-  if (N <= 0 || C <= 0 || H < ML_MIN_SIZE || W < ML_MIN_SIZE) return -1;
+  if (N <= 0 || C <= 0 || H < ssim::MIN_SIZE || W < ssim::MIN_SIZE) return -1;
   const long long lim = (1LL << 31) - 1;
   if ((long long)H * W > (1LL << 24)) return -1;         // in-plane offsets are ints, and the map counts are exact in fp32
   g->planes = (long long)N * C;
-  g->h[0] = H; g->w[0] = W;
-  for (int k = 1; k < ML_LEVELS; ++k) {
-    const int p = (g->h[k - 1] % 2) | (g->w[k - 1] % 2);
-    g->h[k] = (g->h[k - 1] + p) / 2;
-    g->w[k] = (g->w[k - 1] + p) / 2;
-  }
+  ssim::level_sizes(H, W, g->h, g->w);
   int t = 0;
   long long most = 1;                                    // the most blocks per plane of any launch
   for (int k = 0; k < ML_LEVELS; ++k) {
     g->first[k] = t;
-    t += ((g->w[k] - ML_HALO + ML_FT - 1) / ML_FT) * ((g->h[k] - ML_HALO + ML_FT - 1) / ML_FT);
+    t += ssim::map_tiles(g->h[k], g->w[k]);
     g->btx[k] = (g->w[k] + ML_BTX - 1) / ML_BTX;
     g->bty[k] = (g->h[k] + ML_BTY - 1) / ML_BTY;
     const long long b = (long long)g->btx[k] * g->bty[k], pool = ((long long)g->h[k] * g->w[k] + ML_THREADS - 1) / ML_THREADS;
@@ -409,9 +347,7 @@ static int ml_geometry(int N, int C, int H, int W, MlGeom* g) {
 extern "C" long long srk_ms_ssim_loss_workspace_bytes(int N, int C, int H, int W) {
   MlGeom g;
   if (ml_geometry(N, C, H, W, &g)) return -1;
-  long long floats = 0;
-  for (int k = 1; k < ML_LEVELS; ++k) floats += 2LL * g.planes * g.h[k] * g.w[k];
-  return (floats * 4 + 255) / 256 * 256;
+  return ssim::workspace_bytes(g.planes, g.h, g.w);
 }
 
 extern "C" int srk_ms_ssim_loss_tiles(int N, int C, int H, int W, int* first) {
@@ -426,27 +362,8 @@ static int ml_check(const srk_ms_ssim_loss_args* a, const char* who, MlGeom* g) 
   SRK_CHECK_ARG(a, "%s: null pointer", who);
   SRK_CHECK_ARG(ml_geometry(a->N, a->C, a->H, a->W, g) == 0,
                 "%s: %dx%dx%dx%d refused (N, C > 0, H and W at least %d, and planes x tiles must stay below 2^31)", who, a->N, a->C,
-                a->H, a->W, ML_MIN_SIZE);
+                a->H, a->W, ssim::MIN_SIZE);
   return 0;
-}
-
-// the pyramid's levels in the workspace: level k >= 1 of x, then of y
-static void ml_levels(const srk_ms_ssim_loss_args* a, const MlGeom& g, MlLevel (&lv)[ML_LEVELS]) {
-  lv[0].x = a->sr;
-  lv[0].y = a->hr;
-  float* ws = a->workspace;
-  for (int k = 0; k < ML_LEVELS; ++k) {
-    if (k > 0) {
-      const size_t n = (size_t)g.planes * g.h[k] * g.w[k];
-      lv[k].x = ws;
-      lv[k].y = ws + n;
-      ws += 2 * n;
-    }
-    lv[k].H = g.h[k];
-    lv[k].W = g.w[k];
-    lv[k].tilesX = (g.w[k] - ML_HALO + ML_FT - 1) / ML_FT;
-    lv[k].first = g.first[k];
-  }
 }
 
 extern "C" int srk_ms_ssim_loss_fwd(const srk_ms_ssim_loss_args* a, srk_stream_t stream) {
@@ -456,11 +373,10 @@ extern "C" int srk_ms_ssim_loss_fwd(const srk_ms_ssim_loss_args* a, srk_stream_t
   SRK_CHECK_ARG((uintptr_t)a->partials % 16 == 0 && (uintptr_t)a->workspace % 4 == 0, "srk_ms_ssim_loss_fwd: workspace alignment");
   const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   MlMapsArgs m;
-  ml_levels(a, g, m.lv);
-  m.tiles = g.first[ML_LEVELS];
+  m.tiles = ssim::layout_levels(a->sr, a->hr, a->workspace, g.planes, g.h, g.w, m.lv);
   m.partials = a->partials;
   for (int k = 1; k < ML_LEVELS; ++k) {
-    const int p = (g.h[k - 1] % 2) | (g.w[k - 1] % 2);
+    const int p = ssim::level_pad(g.h[k - 1], g.w[k - 1]);
     const int bpp = (g.h[k] * g.w[k] + ML_THREADS - 1) / ML_THREADS;
     hipLaunchKernelGGL(ml_pool_kernel, dim3((unsigned)(g.planes * bpp)), dim3(ML_THREADS), 0, s, m.lv[k - 1].x, m.lv[k - 1].y, g.h[k - 1],
                        g.w[k - 1], const_cast<float*>(m.lv[k].x), const_cast<float*>(m.lv[k].y), g.h[k], g.w[k], p, bpp, k == 1 ? 1 : 0);
@@ -480,7 +396,7 @@ extern "C" int srk_ms_ssim_loss_finalize(const srk_ms_ssim_loss_args* a, srk_str
   f.partials = a->partials;
   for (int k = 0; k <= ML_LEVELS; ++k) f.first[k] = g.first[k];
   for (int k = 0; k < ML_LEVELS; ++k) {
-    f.count[k] = (float)((g.h[k] - ML_HALO) * (g.w[k] - ML_HALO));
+    f.count[k] = (float)((g.h[k] - HALO) * (g.w[k] - HALO));
     f.weight[k] = (float)kMlWeight[k];
   }
   f.planes = (int)g.planes;
@@ -496,8 +412,8 @@ extern "C" int srk_ms_ssim_loss_bwd(const srk_ms_ssim_loss_args* a, srk_stream_t
   if (int rc = ml_check(a, "srk_ms_ssim_loss_bwd", &g)) return rc;
   SRK_CHECK_ARG(a->sr && a->hr && a->workspace && a->table && a->gout && a->gwork && a->grad, "srk_ms_ssim_loss_bwd: null pointer");
   const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  MlLevel lv[ML_LEVELS];
-  ml_levels(a, g, lv);
+  ssim::Level lv[ML_LEVELS];
+  ssim::layout_levels(a->sr, a->hr, a->workspace, g.planes, g.h, g.w, lv);
   // the gradients of levels 1-4 of x in gwork, in level order
   float* gl[ML_LEVELS];
   gl[0] = a->grad;
@@ -519,7 +435,7 @@ extern "C" int srk_ms_ssim_loss_bwd(const srk_ms_ssim_loss_args* a, srk_stream_t
     b.gpar = last ? nullptr : gl[k + 1];
     b.Hn = last ? 0 : g.h[k + 1];
     b.Wn = last ? 0 : g.w[k + 1];
-    b.p = (g.h[k] % 2) | (g.w[k] % 2);
+    b.p = ssim::level_pad(g.h[k], g.w[k]);
     b.gdst = gl[k];
     b.tiles_x = g.btx[k];
     b.tiles_pp = g.btx[k] * g.bty[k];

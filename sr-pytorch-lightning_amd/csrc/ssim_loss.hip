@@ -1,9 +1,9 @@
 // SSIM loss, 1 - SSIM(clamp(sr, 0, 1), hr) with piq.ssim's defaults (piq.SSIMLoss; the metric twin is ssim_kernel in data.hip):
-// include/srk.h "SSIM loss", sr_amd/ssim_loss.py.  One (image, channel) plane at a time; "pooled" pixels are the f x f means.
+// include/srk.h "SSIM loss", sr_amd/ssim_loss.py.  The constants, the moment passes and the map value are ssim_core.h's.  One
+// (image, channel) plane at a time; "pooled" pixels are the f x f means.
 //   ssim_loss_fwd_kernel       one workgroup per (plane, 16x16 tile of the valid SSIM map): clamp sr, pool both images into LDS
-//                              (26x26 pooled pixels), the horizontal 11-tap pass of the five moments (x, y, xx, yy, xy), the
-//                              vertical pass and the SSIM formula per position, and the tile's sum as one double in its own slot
-//                              (no atomics: bitwise repeatable).
+//                              (26x26 pooled pixels), the moments and the SSIM value per position, and the tile's sum as one
+//                              double in its own slot (no atomics: bitwise repeatable).
 //   ssim_loss_finalize_kernel  one workgroup: the fixed-order fp64 sum of every tile, loss = 1 - sum / (N C (Hp-10)(Wp-10)).
 //   ssim_loss_bwd_kernel       one workgroup per (plane, 16x32 tile of pooled sr pixels): recomputes the moments of the 26x42 map
 //                              positions whose windows touch the tile from a 36x52 haloed tile of both images, the adjoints
@@ -16,26 +16,16 @@
 //   saved maps:          forward reads 8 B and writes m, a, b (12 B);  backward reads m, a, b (12 B), sr and hr (8 B: the 2x and y
 //                        factors and the clamp mask), writes 4 B  -> 20 B + 24 B = 44 B, and 12 B per pixel stay allocated.
 // The recompute costs the backward about 3.7x the forward's filter arithmetic per pixel (the 36x52 region over the 16x32 tile).
-// Plain fp32 VALU (no MFMA: 11-tap separable filters).  The library builds with -ffp-contract=off.
-#include "srk_common.h"
+#include "ssim_core.h"
 
 namespace {
 
+using ssim::HALO;
 constexpr int SL_THREADS = 256;
-constexpr int SL_K = 11, SL_HALO = SL_K - 1;          // Gaussian taps; a valid map of (Hp - 10) x (Wp - 10) positions
 constexpr int FT = 16;                                // forward tile edge, map positions
 constexpr int BTY = 16, BTX = 32;                     // backward tile, pooled pixels
 constexpr int FIN_THREADS = 1024;
-constexpr float SL_C1 = 1e-4f, SL_C2 = 9e-4f;         // (0.01)^2, (0.03)^2: data range 1
-// Both images are held and filtered as x - 1/2, y - 1/2 and the means get the 1/2 back: the (co)variances do not see a shift, and
-// G*x'^2 - (G*x')^2 loses up to four times fewer digits to cancellation on values in [-1/2, 1/2] than on [0, 1] (bright flat
-// areas, where s_xx + s_yy + c2 is about c2, are the worst case).  The gradient is the shifted form's, which is the same function.
-constexpr float SL_SHIFT = 0.5f;
 static_assert(FT * FT == SL_THREADS, "forward: one thread per map position");
-// exp(-(k - 5)^2 / (2 * 1.5^2)) / sum, rounded from float64
-__device__ __constant__ float kG[SL_K] = {0.001028380123898387f, 0.0075987582094967365f, 0.036000773310661316f, 0.10936068743467331f,
-                                          0.21300554275512695f,  0.26601171493530273f,   0.21300554275512695f,  0.10936068743467331f,
-                                          0.036000773310661316f, 0.0075987582094967365f, 0.001028380123898387f};
 
 // RY x RX pooled pixels of one plane of both images, top-left pooled pixel (oy, ox): x' = mean of clamp(sr, 0, 1) - 1/2, y' = mean of
 // hr - 1/2 over the f x f block; zero outside [0, Hp) x [0, Wp) (such pixels only reach map positions that are not valid)
@@ -54,47 +44,17 @@ SRK_DEV void load_region(const float* xs, const float* ys, int W, int f, int oy,
           vx += fminf(fmaxf(xs[o], 0.f), 1.f);
           vy += ys[o];
         }
-      vx = vx * inv - SL_SHIFT;
-      vy = vy * inv - SL_SHIFT;
+      vx = vx * inv - ssim::SHIFT;
+      vy = vy * inv - ssim::SHIFT;
     }
     X[r][c] = vx;
     Y[r][c] = vy;
   }
 }
 
-// horizontal pass: Hm[q][r][c] = sum_k G[k] * moment_q(r, c + k) for the RY rows and the RX - 10 columns
-template <int RY, int RX>
-SRK_DEV void moments_rows(const float (*X)[RX + 1], const float (*Y)[RX + 1], float (*Hm)[RY][RX - SL_HALO]) {
-  constexpr int SX = RX - SL_HALO;
-  for (int i = threadIdx.x; i < RY * SX; i += SL_THREADS) {
-    const int r = i / SX, c = i - r * SX;
-    float m[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int k = 0; k < SL_K; ++k) {
-      const float xv = X[r][c + k], yv = Y[r][c + k], w = kG[k];
-      m[0] += w * xv; m[1] += w * yv; m[2] += w * (xv * xv); m[3] += w * (yv * yv); m[4] += w * (xv * yv);
-    }
-#pragma unroll
-    for (int q = 0; q < 5; ++q) Hm[q][r][c] = m[q];
-  }
-}
-
-// vertical pass at map position (r, c) of the tile: G*x', G*y', G*x'x', G*y'y', G*x'y'
-template <int RY, int SX>
-SRK_DEV void moments_at(const float (*Hm)[RY][SX], int r, int c, float m[5]) {
-#pragma unroll
-  for (int q = 0; q < 5; ++q) m[q] = 0.f;
-#pragma unroll
-  for (int k = 0; k < SL_K; ++k) {
-    const float w = kG[k];
-#pragma unroll
-    for (int q = 0; q < 5; ++q) m[q] += w * Hm[q][r + k][c];
-  }
-}
-
 __global__ __launch_bounds__(SL_THREADS) void ssim_loss_fwd_kernel(const srk_ssim_loss_args a, int f, int Hp, int Wp, int tiles_x,
                                                                     int tiles_pp) {
-  constexpr int R = FT + SL_HALO;
+  constexpr int R = FT + HALO;
   __shared__ float X[R][R + 1], Y[R][R + 1];
   __shared__ float Hm[5][R][FT];
   __shared__ double red[SL_THREADS / 64];
@@ -104,17 +64,14 @@ __global__ __launch_bounds__(SL_THREADS) void ssim_loss_fwd_kernel(const srk_ssi
   const size_t po = (size_t)plane * a.H * a.W;
   load_region<R, R>(a.sr + po, a.hr + po, a.W, f, y0, x0, Hp, Wp, X, Y);
   __syncthreads();
-  moments_rows<R, R>(X, Y, Hm);
+  ssim::moments_rows<SL_THREADS, R, R>(X, Y, Hm);
   __syncthreads();
   const int r = tid / FT, c = tid % FT;
   double acc = 0.0;
-  if (y0 + r + SL_HALO < Hp && x0 + c + SL_HALO < Wp) {
+  if (y0 + r + HALO < Hp && x0 + c + HALO < Wp) {
     float m[5];
-    moments_at<R, FT>(Hm, r, c, m);
-    const float sxx = m[2] - m[0] * m[0], syy = m[3] - m[1] * m[1], sxy = m[4] - m[0] * m[1];
-    const float mx = m[0] + SL_SHIFT, my = m[1] + SL_SHIFT;
-    const float cs = (2.f * sxy + SL_C2) / (sxx + syy + SL_C2);
-    acc = (double)((2.f * mx * my + SL_C1) / (mx * mx + my * my + SL_C1) * cs);
+    ssim::moments_at<R, FT>(Hm, r, c, m);
+    acc = (double)ssim::map_values(m).ss;
   }
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
@@ -150,8 +107,8 @@ __global__ __launch_bounds__(FIN_THREADS) void ssim_loss_finalize_kernel(const s
 
 __global__ __launch_bounds__(SL_THREADS) void ssim_loss_bwd_kernel(const srk_ssim_loss_args a, int f, int Hp, int Wp, int tiles_x,
                                                                     int tiles_pp, float scale) {
-  constexpr int SY = BTY + SL_HALO, SX = BTX + SL_HALO;          // map positions whose windows touch the tile
-  constexpr int RY = SY + SL_HALO, RX = SX + SL_HALO;            // pooled pixels those positions read
+  constexpr int SY = BTY + HALO, SX = BTX + HALO;                // map positions whose windows touch the tile
+  constexpr int RY = SY + HALO, RX = SX + HALO;                  // pooled pixels those positions read
   __shared__ float X[RY][RX + 1], Y[RY][RX + 1];
   __shared__ float Hm[5][RY][SX];
   __shared__ float adj[3][SY][SX + 1];                           // m, a, b of the map positions (0 where not valid)
@@ -162,22 +119,22 @@ __global__ __launch_bounds__(SL_THREADS) void ssim_loss_bwd_kernel(const srk_ssi
   const int i0 = (t / tiles_x) * BTY, j0 = (t % tiles_x) * BTX;  // the tile's first pooled pixel
   const size_t po = (size_t)plane * a.H * a.W;
   // region pixel (r, c) is pooled pixel (i0 - 10 + r, j0 - 10 + c); map position (r, c) of the tile is (i0 - 10 + r, j0 - 10 + c) too
-  load_region<RY, RX>(a.sr + po, a.hr + po, a.W, f, i0 - SL_HALO, j0 - SL_HALO, Hp, Wp, X, Y);
+  load_region<RY, RX>(a.sr + po, a.hr + po, a.W, f, i0 - HALO, j0 - HALO, Hp, Wp, X, Y);
   __syncthreads();
-  moments_rows<RY, RX>(X, Y, Hm);
+  ssim::moments_rows<SL_THREADS, RY, RX>(X, Y, Hm);
   __syncthreads();
   for (int i = tid; i < SY * SX; i += SL_THREADS) {
     const int r = i / SX, c = i - r * SX;
-    const int pi = i0 - SL_HALO + r, pj = j0 - SL_HALO + c;
+    const int pi = i0 - HALO + r, pj = j0 - HALO + c;
     float gm = 0.f, ga = 0.f, gb = 0.f;
-    if (pi >= 0 && pi + SL_HALO < Hp && pj >= 0 && pj + SL_HALO < Wp) {
+    if (pi >= 0 && pi + HALO < Hp && pj >= 0 && pj + HALO < Wp) {
       float m[5];
-      moments_at<RY, SX>(Hm, r, c, m);
+      ssim::moments_at<RY, SX>(Hm, r, c, m);
       const float ux = m[0], uy = m[1];                          // the shifted means: what s_xx, s_xy see
-      const float mx = ux + SL_SHIFT, my = uy + SL_SHIFT;
+      const float mx = ux + ssim::SHIFT, my = uy + ssim::SHIFT;
       const float sxx = m[2] - ux * ux, syy = m[3] - uy * uy, sxy = m[4] - ux * uy;
-      const float ib1 = 1.f / (mx * mx + my * my + SL_C1), ib2 = 1.f / (sxx + syy + SL_C2);
-      const float l = (2.f * mx * my + SL_C1) * ib1, cs = (2.f * sxy + SL_C2) * ib2;      // S = l * cs
+      const float ib1 = 1.f / (mx * mx + my * my + ssim::C1), ib2 = 1.f / (sxx + syy + ssim::C2);
+      const float l = (2.f * mx * my + ssim::C1) * ib1, cs = (2.f * sxy + ssim::C2) * ib2;      // S = l * cs
       ga = -(l * cs) * ib2;                                      // through sigma_xx
       gb = 2.f * l * ib2;                                        // through sigma_xy
       // d S / d (G*x') in full: 2 mu_y cs / B1 - 2 mu_x S / B1 - u_y b - 2 u_x a, grouped so that each difference is taken once
@@ -193,8 +150,8 @@ __global__ __launch_bounds__(SL_THREADS) void ssim_loss_bwd_kernel(const srk_ssi
     const int r = i / BTX, c = i - r * BTX;
     float v[3] = {0.f, 0.f, 0.f};
 #pragma unroll
-    for (int k = 0; k < SL_K; ++k) {
-      const float w = kG[k];
+    for (int k = 0; k < ssim::K; ++k) {
+      const float w = ssim::kG[k];
 #pragma unroll
       for (int q = 0; q < 3; ++q) v[q] += w * adj[q][r][c + k];
     }
@@ -211,12 +168,12 @@ __global__ __launch_bounds__(SL_THREADS) void ssim_loss_bwd_kernel(const srk_ssi
     if (pi >= Hp || pj >= Wp) continue;
     float v[3] = {0.f, 0.f, 0.f};
 #pragma unroll
-    for (int k = 0; k < SL_K; ++k) {
-      const float w = kG[k];
+    for (int k = 0; k < ssim::K; ++k) {
+      const float w = ssim::kG[k];
 #pragma unroll
       for (int q = 0; q < 3; ++q) v[q] += w * Ha[q][r + k][c];
     }
-    const float x = X[r + SL_HALO][c + SL_HALO], y = Y[r + SL_HALO][c + SL_HALO];      // x', y': the shifted pixels
+    const float x = X[r + HALO][c + HALO], y = Y[r + HALO][c + HALO];            // x', y': the shifted pixels
     const float g = (v[0] + 2.f * x * v[1] + y * v[2]) * gs;
     for (int dy = 0; dy < f; ++dy)
       for (int dx = 0; dx < f; ++dx) {
@@ -247,9 +204,9 @@ static int sl_geometry(int N, int C, int H, int W, SlGeom* g) {
   g->f = sl_pool(H, W);
   g->Hp = H / g->f;
   g->Wp = W / g->f;
-  if (g->Hp < SL_K || g->Wp < SL_K) return -1;
-  g->ftx = (g->Wp - SL_HALO + FT - 1) / FT;
-  g->fty = (g->Hp - SL_HALO + FT - 1) / FT;
+  if (g->Hp < ssim::K || g->Wp < ssim::K) return -1;
+  g->ftx = (g->Wp - HALO + FT - 1) / FT;
+  g->fty = (g->Hp - HALO + FT - 1) / FT;
   g->btx = (g->Wp + BTX - 1) / BTX;
   g->bty = (g->Hp + BTY - 1) / BTY;
   g->planes = (long long)N * C;
@@ -289,7 +246,7 @@ extern "C" int srk_ssim_loss_finalize(const srk_ssim_loss_args* a, srk_stream_t 
   SlGeom g;
   if (int rc = sl_check(a, "srk_ssim_loss_finalize", &g)) return rc;
   SRK_CHECK_ARG(a->partial && a->loss, "srk_ssim_loss_finalize: null pointer");
-  const double count = (double)g.planes * (double)(g.Hp - SL_HALO) * (double)(g.Wp - SL_HALO);
+  const double count = (double)g.planes * (double)(g.Hp - HALO) * (double)(g.Wp - HALO);
   hipLaunchKernelGGL(ssim_loss_finalize_kernel, dim3(1), dim3(FIN_THREADS), 0, reinterpret_cast<hipStream_t>(stream), *a,
                      g.planes * g.ftx * g.fty, count);
   SRK_LAUNCH_CHECK();
@@ -301,7 +258,7 @@ extern "C" int srk_ssim_loss_bwd(const srk_ssim_loss_args* a, srk_stream_t strea
   if (int rc = sl_check(a, "srk_ssim_loss_bwd", &g)) return rc;
   SRK_CHECK_ARG(a->hr && a->gout && a->grad, "srk_ssim_loss_bwd: null pointer");
   const int tpp = g.btx * g.bty;
-  const double count = (double)g.planes * (double)(g.Hp - SL_HALO) * (double)(g.Wp - SL_HALO);
+  const double count = (double)g.planes * (double)(g.Hp - HALO) * (double)(g.Wp - HALO);
   const float scale = (float)(-1.0 / (count * (double)g.f * (double)g.f));
   hipLaunchKernelGGL(ssim_loss_bwd_kernel, dim3((unsigned)(g.planes * tpp)), dim3(SL_THREADS), 0, reinterpret_cast<hipStream_t>(stream),
                      *a, g.f, g.Hp, g.Wp, g.btx, tpp, scale);

@@ -34,7 +34,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib as L
-from .ops import _f32c, _need_gpu, _stream      # (ops.py imports this module at its END: these exist by then)
+from .ops import _f32c, _need_gpu, _ptr, _stream      # (ops.py imports this module at its END: these exist by then)
 
 __all__ = ["flip_tables", "flip_torch", "flip_error_map_torch", "FlipLossFn", "flip_loss", "flip_error_map", "flip"]
 
@@ -283,9 +283,8 @@ def _device_table_for(device):
 
 def _args(s, h, tab, *, partial=None, err=None, adj=None, gout=None, scale=0.0, grad=None):
     n, _, hh, ww = s.shape
-    p = lambda t: 0 if t is None else t.data_ptr()         # noqa: E731
-    return L.FlipArgs(sr=s.data_ptr(), hr=p(h), N=n, H=hh, W=ww, table=tab.data_ptr(), partial=p(partial), err=p(err), adj=p(adj),
-                      gout=p(gout), scale=float(scale), grad=p(grad))
+    return L.FlipArgs(sr=s.data_ptr(), hr=_ptr(h), N=n, H=hh, W=ww, table=tab.data_ptr(), partial=_ptr(partial), err=_ptr(err),
+                      adj=_ptr(adj), gout=_ptr(gout), scale=float(scale), grad=_ptr(grad))
 
 
 def _forward(sr, hr, want_map, want_adj):

@@ -30,7 +30,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib as L
-from .ops import _f32c, _need_gpu, _stream      # (ops.py imports this module at its END: these exist by then)
+from .ops import _f32c, _need_gpu, _ptr, _stream      # (ops.py imports this module at its END: these exist by then)
 
 __all__ = ["gmsd_torch", "GMSDLossFn", "gmsd_loss", "gmsd"]
 
@@ -89,9 +89,8 @@ def gmsd_torch(x, y):
 # --------------------------------------------------------------------------------------------
 def _args(s, h, *, partial=None, stats=None, loss=None, gout=None, grad=None):
     n, c, hh, ww = s.shape
-    p = lambda t: 0 if t is None else t.data_ptr()         # noqa: E731
-    return L.GmsdArgs(sr=s.data_ptr(), hr=h.data_ptr(), N=n, C=c, H=hh, W=ww, partial=p(partial), stats=p(stats), loss=p(loss),
-                      gout=p(gout), grad=p(grad))
+    return L.GmsdArgs(sr=s.data_ptr(), hr=h.data_ptr(), N=n, C=c, H=hh, W=ww, partial=_ptr(partial), stats=_ptr(stats),
+                      loss=_ptr(loss), gout=_ptr(gout), grad=_ptr(grad))
 
 
 def _forward(s, h):

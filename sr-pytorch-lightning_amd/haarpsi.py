@@ -27,7 +27,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib as L
-from .ops import _f32c, _need_gpu, _stream      # (ops.py imports this module at its END: these exist by then)
+from .ops import _f32c, _need_gpu, _ptr, _stream      # (ops.py imports this module at its END: these exist by then)
 
 __all__ = ["haarpsi_torch", "HaarPSILossFn", "haarpsi_loss", "haarpsi"]
 
@@ -101,9 +101,8 @@ def haarpsi_torch(x, y):
 # --------------------------------------------------------------------------------------------
 def _args(s, h, *, partial, planes, stats, loss=None, index=None, gout=None, grad=None):
     n, c, hh, ww = s.shape
-    p = lambda t: 0 if t is None else t.data_ptr()         # noqa: E731
-    return L.HaarpsiArgs(sr=s.data_ptr(), hr=p(h), N=n, C=c, H=hh, W=ww, partial=p(partial), planes=p(planes), stats=p(stats),
-                         loss=p(loss), index=p(index), gout=p(gout), grad=p(grad))
+    return L.HaarpsiArgs(sr=s.data_ptr(), hr=_ptr(h), N=n, C=c, H=hh, W=ww, partial=_ptr(partial), planes=_ptr(planes),
+                         stats=_ptr(stats), loss=_ptr(loss), index=_ptr(index), gout=_ptr(gout), grad=_ptr(grad))
 
 
 def _forward(sr, hr, want_index, want_planes):

@@ -23,15 +23,11 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib as L
-from .ops import _f32c, _need_gpu, _stream      # (ops.py imports this module at its END: these exist by then)
+from .ops import _f32c, _need_gpu, _ptr, _stream      # (ops.py imports this module at its END: these exist by then)
 from .ops_metrics import MS_SSIM_WEIGHTS, ms_ssim_check
+from .ssim_loss import C1, C2, SHIFT, _hip_ok, _moments      # (ops.py imports ssim_loss before this module)
 
 __all__ = ["ms_ssim_torch", "MSSSIMLossFn", "ms_ssim_loss"]
-
-KERNEL_SIZE, SIGMA, C1, C2 = 11, 1.5, 0.01 ** 2, 0.03 ** 2
-# Both paths filter x - 1/2 and y - 1/2 and give the means the 1/2 back (ssim_loss.SHIFT): the (co)variances do not see a shift, and
-# in fp32 G*x'^2 - (G*x')^2 then loses several times fewer digits to cancellation on images in [0, 1].
-SHIFT = 0.5
 
 
 def ms_ssim_torch(x, y):
@@ -42,9 +38,6 @@ def ms_ssim_torch(x, y):
     ms_ssim_check(x, y)
     dt = x.dtype if x.dtype in (torch.float32, torch.float64) else torch.float32
     x, y = x.to(dt), y.to(dt)
-    co = torch.arange(KERNEL_SIZE, dtype=dt, device=x.device) - (KERNEL_SIZE - 1) / 2.0
-    g = torch.exp(-(co ** 2) / (2 * SIGMA ** 2))
-    g = g / g.sum()
     means = []
     last = len(MS_SSIM_WEIGHTS) - 1
     for level in range(last + 1):
@@ -52,11 +45,7 @@ def ms_ssim_torch(x, y):
             p = max(x.shape[-2] % 2, x.shape[-1] % 2)
             x = F.avg_pool2d(F.pad(x, [p, 0, p, 0], mode="replicate"), 2)
             y = F.avg_pool2d(F.pad(y, [p, 0, p, 0], mode="replicate"), 2)
-        n, c, h, w = x.shape
-        xs, ys = x - SHIFT, y - SHIFT
-        z = torch.stack((xs, ys, xs * xs, ys * ys, xs * ys)).reshape(5 * n * c, 1, h, w)
-        z = F.conv2d(F.conv2d(z, g.view(1, 1, 1, -1)), g.view(1, 1, -1, 1))
-        mx, my, xx, yy, xy = z.reshape(5, n, c, h - KERNEL_SIZE + 1, w - KERNEL_SIZE + 1)
+        mx, my, xx, yy, xy = _moments(x, y)
         sxx, syy, sxy = xx - mx * mx, yy - my * my, xy - mx * my
         m = (2 * sxy + C2) / (sxx + syy + C2)
         if level == last:
@@ -76,9 +65,9 @@ def ms_ssim_torch(x, y):
 # --------------------------------------------------------------------------------------------
 def _args(s, h, *, workspace=None, partials=None, table=None, loss=None, gout=None, gwork=None, grad=None):
     n, c, hh, ww = s.shape
-    p = lambda t: 0 if t is None else t.data_ptr()         # noqa: E731
-    return L.MsSsimLossArgs(sr=s.data_ptr(), hr=h.data_ptr(), N=n, C=c, H=hh, W=ww, workspace=p(workspace), partials=p(partials),
-                            table=p(table), loss=p(loss), gout=p(gout), gwork=p(gwork), grad=p(grad))
+    return L.MsSsimLossArgs(sr=s.data_ptr(), hr=h.data_ptr(), N=n, C=c, H=hh, W=ww, workspace=_ptr(workspace),
+                            partials=_ptr(partials), table=_ptr(table), loss=_ptr(loss), gout=_ptr(gout), gwork=_ptr(gwork),
+                            grad=_ptr(grad))
 
 
 class MSSSIMLossFn(torch.autograd.Function):
@@ -118,11 +107,6 @@ class MSSSIMLossFn(torch.autograd.Function):
         grad = torch.empty_like(s)
         L.call("srk_ms_ssim_loss_bwd", _args(s, h, workspace=pyramid, table=table, gout=gout, gwork=gwork, grad=grad), _stream())
         return grad, None
-
-
-def _hip_ok(sr, hr):
-    return (sr.is_cuda and hr.is_cuda and sr.dtype == torch.float32 and hr.dtype == torch.float32 and sr.dim() == 4
-            and sr.shape == hr.shape and sr.numel() > 0 and sr.is_contiguous() and hr.is_contiguous())
 
 
 def ms_ssim_loss(sr, hr):

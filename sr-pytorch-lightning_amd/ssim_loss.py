@@ -21,7 +21,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib as L
-from .ops import _f32c, _need_gpu, _stream      # (ops.py imports this module at its END: these exist by then)
+from .ops import _f32c, _need_gpu, _ptr, _stream      # (ops.py imports this module at its END: these exist by then)
 
 __all__ = ["ssim_torch", "SSIMLossFn", "ssim_loss"]
 
@@ -47,6 +47,19 @@ def _check(x, y):
     return f
 
 
+def _moments(x, y):
+    """G*x', G*y', G*x'x', G*y'y', G*x'y' of x' = x - 1/2, y' = y - 1/2 over the valid map: the Gaussian applied as a row pass and a
+    column pass over the five moment planes at once."""
+    n, c, h, w = x.shape
+    co = torch.arange(KERNEL_SIZE, dtype=x.dtype, device=x.device) - (KERNEL_SIZE - 1) / 2.0
+    g = torch.exp(-(co ** 2) / (2 * SIGMA ** 2))
+    g = g / g.sum()
+    xs, ys = x - SHIFT, y - SHIFT
+    z = torch.stack((xs, ys, xs * xs, ys * ys, xs * ys)).reshape(5 * n * c, 1, h, w)
+    z = F.conv2d(F.conv2d(z, g.view(1, 1, 1, -1)), g.view(1, 1, -1, 1))
+    return z.reshape(5, n, c, h - KERNEL_SIZE + 1, w - KERNEL_SIZE + 1)
+
+
 def ssim_torch(x, y):
     """SSIM (mean over images, 0-d) of test image `x` against reference `y` in plain torch (fp32 or float64, any device), the
     Gaussian applied as a row pass and a column pass over the five moment planes (of x - 1/2, y - 1/2) at once.  No clamp: `ssim_loss` clamps sr as the
@@ -56,14 +69,7 @@ def ssim_torch(x, y):
     x, y = x.to(dt), y.to(dt)
     if f > 1:
         x, y = F.avg_pool2d(x, f), F.avg_pool2d(y, f)
-    n, c, h, w = x.shape
-    co = torch.arange(KERNEL_SIZE, dtype=dt, device=x.device) - (KERNEL_SIZE - 1) / 2.0
-    g = torch.exp(-(co ** 2) / (2 * SIGMA ** 2))
-    g = g / g.sum()
-    xs, ys = x - SHIFT, y - SHIFT
-    z = torch.stack((xs, ys, xs * xs, ys * ys, xs * ys)).reshape(5 * n * c, 1, h, w)
-    z = F.conv2d(F.conv2d(z, g.view(1, 1, 1, -1)), g.view(1, 1, -1, 1))
-    mx, my, xx, yy, xy = z.reshape(5, n, c, h - KERNEL_SIZE + 1, w - KERNEL_SIZE + 1)
+    mx, my, xx, yy, xy = _moments(x, y)
     sxx, syy, sxy = xx - mx * mx, yy - my * my, xy - mx * my
     mx, my = mx + SHIFT, my + SHIFT
     s = (2 * mx * my + C1) * (2 * sxy + C2) / ((mx * mx + my * my + C1) * (sxx + syy + C2))
@@ -75,9 +81,8 @@ def ssim_torch(x, y):
 # --------------------------------------------------------------------------------------------
 def _args(s, h, *, partial=None, loss=None, gout=None, grad=None):
     n, c, hh, ww = s.shape
-    p = lambda t: 0 if t is None else t.data_ptr()         # noqa: E731
-    return L.SsimLossArgs(sr=s.data_ptr(), hr=h.data_ptr(), N=n, C=c, H=hh, W=ww, partial=p(partial), loss=p(loss), gout=p(gout),
-                          grad=p(grad))
+    return L.SsimLossArgs(sr=s.data_ptr(), hr=h.data_ptr(), N=n, C=c, H=hh, W=ww, partial=_ptr(partial), loss=_ptr(loss), gout=_ptr(gout),
+                          grad=_ptr(grad))
 
 
 class SSIMLossFn(torch.autograd.Function):
