@@ -16,14 +16,13 @@ GPU parameters always take the HIP kernel and raise if the library is missing.  
 recurrence in torch ops and swap by value.
 """
 import contextlib
-import ctypes as C
 from collections import OrderedDict
 
 import numpy as np
 import torch
 
 from . import _lib as L
-from .optim import _CHUNK
+from .optim import _Table
 
 
 def _weight(decay):
@@ -77,7 +76,9 @@ class ParamEMA:
         self.set_decay(decay)
         if self.on_gpu:
             L.load()                                         # raises when the library is missing: there is no torch path on the GPU
-            self._build_table()
+            # the optimizers' device table (optim._Table): `g` unused, `state_off` the offset into `flat`.  Made here, outside any
+            # capture (page-locked allocations are not capturable); store() below uploads it
+            self._table = _Table(_Table.capacity(ps), dev)
         self.store()
 
     # -- state ------------------------------------------------------------------------------------
@@ -103,58 +104,18 @@ class ParamEMA:
         return int(self._count.item())
 
     # -- device table --------------------------------------------------------------------------------
-    def _build_table(self):
-        """Slots and blocks in host memory, the device bytes, the page-locked staging buffer; then the first upload.  Called once,
-        outside any capture (page-locked allocations are not capturable)."""
-        ps = self.params
-        self._slots = (L.AdamSlot * len(ps))()
-        blocks = []
-        for i, p in enumerate(ps):
-            n = p.numel()
-            self._slots[i].g, self._slots[i].state_off, self._slots[i].n, self._slots[i].step_idx = None, self._offsets[p], n, 0
-            for s0 in range(0, n, _CHUNK):
-                blocks.append((i, min(_CHUNK, n - s0), s0))
-        self._nblocks = len(blocks)
-        self._blocks = (L.AdamBlock * max(self._nblocks, 1))()
-        for j, (i, cnt, s0) in enumerate(blocks):
-            self._blocks[j].slot, self._blocks[j].count, self._blocks[j].start = i, cnt, s0
-        ssz = C.sizeof(L.AdamSlot) * len(ps)
-        self._blocks_off = (ssz + 15) // 16 * 16
-        total = self._blocks_off + C.sizeof(L.AdamBlock) * max(self._nblocks, 1)
-        self._table = torch.empty(total, dtype=torch.uint8, device=self.device)
-        self._host = torch.zeros(total, dtype=torch.uint8, pin_memory=True)
-        C.memmove(self._host.data_ptr() + self._blocks_off, C.addressof(self._blocks), C.sizeof(L.AdamBlock) * max(self._nblocks, 1))
-        self._key = self._copied = None
-        self._upload(self._addresses())
-
-    def _addresses(self):
-        return tuple(p.data_ptr() for p in self.params)
-
-    def _upload(self, key):
-        """The parameter addresses into the slots, then slots | blocks to the device in one copy from the staging buffer."""
-        if self._copied is not None:
-            self._copied.synchronize()                       # the previous table may still be on its way out of `_host`
-        for slot, ptr in zip(self._slots, key):
-            slot.p = ptr
-        C.memmove(self._host.data_ptr(), C.addressof(self._slots), C.sizeof(L.AdamSlot) * len(self.params))
-        with torch.cuda.device(self.device):
-            self._table.copy_(self._host, non_blocking=True)
-            self._copied = torch.cuda.Event()
-            self._copied.record()
-        self._copied.synchronize()                           # visible to every stream (a capture runs on a side stream)
-        self._key = key
-
     def _launch(self, op):
-        if self._nblocks == 0:                               # (only empty tensors)
-            return
-        key = self._addresses()
-        if key != self._key:
+        t = self._table
+        key = tuple(p.data_ptr() for p in self.params)
+        if key != t.key:
             if torch.cuda.is_current_stream_capturing():
                 raise RuntimeError("ParamEMA: a parameter's address moved; the device table cannot be rebuilt inside a hipGraph capture")
-            self._upload(key)
-        a = L.EmaArgs(slots=self._table.data_ptr(), blocks=self._table.data_ptr() + self._blocks_off, nslots=len(self.params),
-                      nblocks=self._nblocks, shadow=self.flat.data_ptr(), weight=self._weight.data_ptr(), count=self._count.data_ptr(),
-                      op=op)
+            with torch.cuda.device(self.device):
+                t.fill([(p, None, self._offsets[p], 0) for p in self.params], key)
+            t.copied.synchronize()                           # visible to every stream (a capture runs on a side stream)
+        if t.nblocks == 0:                                   # (only empty tensors)
+            return
+        a = L.EmaArgs(**t.pointers(), shadow=self.flat.data_ptr(), weight=self._weight.data_ptr(), count=self._count.data_ptr(), op=op)
         with torch.cuda.device(self.device):
             L.call("srk_ema_step", a, torch.cuda.current_stream().cuda_stream)
         if op in (L.EMA_SWAP, L.EMA_LOAD):

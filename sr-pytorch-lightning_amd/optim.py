@@ -61,12 +61,13 @@ class DeviceGradScaler:
 
 
 class _Table:
-    """One device copy of the (parameter, gradient) table with its page-locked staging buffer.  The eager steps own one;
-    every hipGraph capture gets ITS OWN (a captured upload is a memcpy node that re-reads the staging buffer on every
-    replay, so nothing an eager step does later may touch the bytes a live graph points at: ADVICE r2)."""
+    """One device copy of a parameter table -- slots | 16-byte gap | blocks (srk_adam_slot / srk_adam_block) -- with its page-locked
+    staging buffer: what every table kernel reads (csrc/param_table.h).  The eager optimizer steps own one and every hipGraph
+    capture gets ITS OWN (a captured upload is a memcpy node that re-reads the staging buffer on every replay, so nothing an eager
+    step does later may touch the bytes a live graph points at: ADVICE r2); `ema.ParamEMA` owns one."""
 
     def __init__(self, cap, dev):
-        self.table = torch.empty(cap, dtype=torch.uint8, device=dev)   # device bytes: slots | blocks
+        self.table = torch.empty(cap, dtype=torch.uint8, device=dev)   # device bytes
         self.host = torch.empty(cap, dtype=torch.uint8, pin_memory=True)
         self.copied = None      # event behind the last eager upload from `host`
         self.key = None
@@ -75,6 +76,58 @@ class _Table:
         self.live_ids = None    # their identities (same set, moved addresses: only the pointer fields are rewritten)
         self.slots = None
         self.nslots = self.nblocks = self.blocks_off = 0
+
+    @staticmethod
+    def capacity(params):
+        """Bytes of the table that holds all of `params`."""
+        return C.sizeof(L.AdamSlot) * len(params) + 16 + C.sizeof(L.AdamBlock) * sum((p.numel() + _CHUNK - 1) // _CHUNK for p in params)
+
+    def fill(self, entries, key, capturing=False):
+        """`entries`: (parameter, gradient or None, offset into the flat state buffers, index of its count) per tensor, in table
+        order; `key`: what the caller compares to decide that the table is stale.  Slots and blocks (one tensor per block of at most
+        _CHUNK elements) are rebuilt when the SET of parameters changed; otherwise only the pointer fields are rewritten.  Then one
+        host-to-device copy from the staging buffer, which was sized when the table was made (so nothing is allocated here):
+        captured into a hipGraph it is ONE memcpy node that replays the same bytes."""
+        ids = tuple(id(p) for p, _, _, _ in entries)
+        same_set = ids == self.live_ids                      # only addresses moved (eager steps re-allocate the gradients)
+        if not same_set:
+            self.slots = (L.AdamSlot * max(len(entries), 1))()
+            blocks = []
+            for i, (p, _, off, idx) in enumerate(entries):
+                n = p.numel()
+                self.slots[i].state_off, self.slots[i].n, self.slots[i].step_idx = off, n, idx
+                for s0 in range(0, n, _CHUNK):
+                    blocks.append((i, min(_CHUNK, n - s0), s0))
+            barr = (L.AdamBlock * max(len(blocks), 1))()
+            for j, (i, cnt, s0) in enumerate(blocks):
+                barr[j].slot, barr[j].count, barr[j].start = i, cnt, s0
+            self.nblocks = len(blocks)
+        slots = self.slots
+        for i, (p, g, _, _) in enumerate(entries):
+            slots[i].p, slots[i].g = p.data_ptr(), (g.data_ptr() if g is not None else None)
+        ssz = C.sizeof(L.AdamSlot) * len(entries)
+        boff = (ssz + 15) // 16 * 16
+        total = boff + C.sizeof(L.AdamBlock) * self.nblocks
+        upto = total if not same_set else ssz                # the block list depends on the sizes only
+        if upto:
+            assert total <= self.host.numel()
+            if self.copied is not None and not capturing:
+                self.copied.synchronize()                    # the previous table may still be on its way out of `host`
+            C.memmove(self.host.data_ptr(), C.addressof(slots), ssz)
+            if not same_set:
+                C.memmove(self.host.data_ptr() + boff, C.addressof(barr), total - boff)
+            self.table[:upto].copy_(self.host[:upto], non_blocking=True)
+            if not capturing:
+                self.copied = torch.cuda.Event()
+                self.copied.record()
+        self.key, self.live_ids = key, ids
+        self.grads, self.live = [g for _, g, _, _ in entries], [p for p, _, _, _ in entries]
+        self.nslots, self.blocks_off = len(entries), boff
+        return self
+
+    def pointers(self):
+        """(slots, blocks, nslots, nblocks): the first four fields of every table kernel's arguments."""
+        return dict(slots=self.table.data_ptr(), blocks=self.table.data_ptr() + self.blocks_off, nslots=self.nslots, nblocks=self.nblocks)
 
 
 class _Plan:
@@ -142,9 +195,7 @@ class _TableStep:
         plan.m, plan.v = plan.flat.get("exp_avg"), plan.flat.get("exp_avg_sq")
         plan.steps = torch.zeros(len(params), dtype=torch.float32, device=dev)
         plan.ticket = torch.zeros(1, dtype=torch.int32, device=dev)
-        # table of the largest case (every parameter has a gradient): tensors | 16-byte gap | blocks
-        cap = C.sizeof(L.AdamSlot) * len(params) + 16 + C.sizeof(L.AdamBlock) * sum((p.numel() + _CHUNK - 1) // _CHUNK for p in params)
-        plan.cap = cap
+        cap = plan.cap = _Table.capacity(params)             # the largest case: every parameter has a gradient
         plan.eager, plan.spare = _Table(cap, dev), _Table(cap, dev)
         host_steps = [0.0] * len(params)
         old_counts = old.steps.tolist() if old is not None else []
@@ -217,43 +268,7 @@ class _TableStep:
                 raise RuntimeError(self._sparse_msg)
             if g.dtype != torch.float32 or not g.is_contiguous() or g.device != p.device or g.numel() != p.numel():
                 raise RuntimeError("HIP %s needs contiguous fp32 gradients on the parameter's device" % type(self).__name__)
-        ids = tuple(id(p) for p, _ in live)
-        same_set = ids == t.live_ids                         # only addresses moved (eager steps re-allocate the gradients)
-        if not same_set:
-            t.slots = (L.AdamSlot * max(len(live), 1))()
-            blocks = []
-            for i, (p, g) in enumerate(live):
-                n = p.numel()
-                t.slots[i].state_off, t.slots[i].n, t.slots[i].step_idx = plan.offsets[p], n, plan.index[p]
-                for s0 in range(0, n, _CHUNK):
-                    blocks.append((i, min(_CHUNK, n - s0), s0))
-            barr = (L.AdamBlock * max(len(blocks), 1))()
-            for j, (i, cnt, s0) in enumerate(blocks):
-                barr[j].slot, barr[j].count, barr[j].start = i, cnt, s0
-            t.nblocks = len(blocks)
-        slots = t.slots
-        for i, (p, g) in enumerate(live):
-            slots[i].p, slots[i].g = p.data_ptr(), g.data_ptr()
-        ssz = C.sizeof(L.AdamSlot) * len(live)
-        boff = (ssz + 15) // 16 * 16
-        total = boff + C.sizeof(L.AdamBlock) * t.nblocks
-        upto = total if not same_set else ssz                # the block list depends on the sizes only
-        if upto:
-            # one host-to-device copy from a page-locked staging buffer sized when the table was made (so nothing is
-            # allocated here): captured into a hipGraph it is ONE memcpy node that replays the same bytes
-            assert total <= t.host.numel()
-            if t.copied is not None and not capturing:
-                t.copied.synchronize()                      # the previous table may still be on its way out of `host`
-            C.memmove(t.host.data_ptr(), C.addressof(slots), ssz)
-            if not same_set:
-                C.memmove(t.host.data_ptr() + boff, C.addressof(barr), total - boff)
-            t.table[:upto].copy_(t.host[:upto], non_blocking=True)
-            if not capturing:
-                t.copied = torch.cuda.Event()
-                t.copied.record()
-        t.key, t.grads, t.live, t.live_ids = key, [g for _, g in live], [p for p, _ in live], ids
-        t.nslots, t.blocks_off = len(live), boff
-        return t
+        return t.fill([(p, g, plan.offsets[p], plan.index[p]) for p, g in live], key, capturing)
 
     # -- step -------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -332,8 +347,7 @@ class Adam(_TableStep, torch.optim.Adam):
 
     def _args(self, plan, t, group):
         b1, b2 = group["betas"]
-        return L.AdamArgs(slots=t.table.data_ptr(), blocks=t.table.data_ptr() + t.blocks_off,
-                          nslots=t.nslots, nblocks=t.nblocks,
+        return L.AdamArgs(**t.pointers(),
                           m=plan.m.data_ptr(), v=plan.v.data_ptr(), steps=plan.steps.data_ptr(), ticket=plan.ticket.data_ptr(),
                           lr=float(group["lr"]), beta1=float(b1), beta2=float(b2), eps=float(group["eps"]),
                           weight_decay=float(group["weight_decay"]), maximize=int(bool(group["maximize"])),
@@ -401,7 +415,7 @@ class SGD(_TableStep, torch.optim.SGD):
 
     def _args(self, plan, t, group):
         mom = float(group["momentum"])
-        return L.SgdArgs(slots=t.table.data_ptr(), blocks=t.table.data_ptr() + t.blocks_off, nslots=t.nslots, nblocks=t.nblocks,
+        return L.SgdArgs(**t.pointers(),
                          buf=plan.flat["momentum_buffer"].data_ptr() if mom != 0 else None, steps=plan.steps.data_ptr(),
                          lr=float(group["lr"]), momentum=mom, dampening=float(group["dampening"]),
                          weight_decay=float(group["weight_decay"]), nesterov=int(bool(group["nesterov"])),
@@ -440,7 +454,7 @@ class RMSprop(_TableStep, torch.optim.RMSprop):
 
     def _args(self, plan, t, group):
         ptr = {key: buf.data_ptr() for key, buf in plan.flat.items()}
-        return L.RmspropArgs(slots=t.table.data_ptr(), blocks=t.table.data_ptr() + t.blocks_off, nslots=t.nslots, nblocks=t.nblocks,
+        return L.RmspropArgs(**t.pointers(),
                              sq=ptr["square_avg"], buf=ptr.get("momentum_buffer"), ga=ptr.get("grad_avg"), steps=plan.steps.data_ptr(),
                              lr=float(group["lr"]), alpha=float(group["alpha"]), eps=float(group["eps"]),
                              weight_decay=float(group["weight_decay"]), momentum=float(group["momentum"]),
@@ -496,7 +510,7 @@ class Ranger(_TableStep, torch.optim.Optimizer):
 
     def _args(self, plan, t, group):
         b1, b2 = group["betas"]
-        return L.RangerArgs(slots=t.table.data_ptr(), blocks=t.table.data_ptr() + t.blocks_off, nslots=t.nslots, nblocks=t.nblocks,
+        return L.RangerArgs(**t.pointers(),
                             m=plan.m.data_ptr(), v=plan.v.data_ptr(), slow=plan.flat["slow_buffer"].data_ptr(),
                             steps=plan.steps.data_ptr(), lr=float(group["lr"]), beta1=float(b1), beta2=float(b2),
                             alpha=float(group["alpha"]), n_sma_threshold=float(group["N_sma_threshhold"]), eps=float(group["eps"]),

@@ -99,7 +99,7 @@ def main():
                          "hip_update_replayed": g_hip.replay, "torch_foreach_lerp_replayed": g_torch.replay,
                          "hip_swap": ema.swap, "torch_swap_per_tensor": torch_swap_each, "torch_swap_foreach": torch_swap_foreach},
                         a.iters, a.repeats)
-        out = {"model": name, "tensors": len(ps), "parameters": n, "blocks": ema._nblocks, "iters": a.iters, "repeats": a.repeats}
+        out = {"model": name, "tensors": len(ps), "parameters": n, "blocks": ema._table.nblocks, "iters": a.iters, "repeats": a.repeats}
         for k, (med, lo, hi) in r.items():
             out[k + "_us"] = round(med, 1)
             out[k + "_min_max_us"] = [round(lo, 1), round(hi, 1)]
