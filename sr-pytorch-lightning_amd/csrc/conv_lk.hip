@@ -1222,6 +1222,15 @@ SRK_DEV void lk5_pair(int t, int& fyA, int& fxA, int& fyB, int& fxB, bool& hasB)
   else { fyA = 2; fxA = t - 12; fyB = 2; fxB = t - 12; hasB = false; }
 }
 
+// The deal of the 14 pairs to the two wave halves: accumulator j of half h holds pair lk5_deal(h, j).  Pair t + 5 (t < 5) at tile row y
+// reads the gradient rows pair t read at row y - 2, at the same columns: the same fragment, lane for lane.  So a pair and its partner
+// sit in the same wave, in accumulators 2k and 2k + 1, and the partner takes its fragment from a register delay line, not from LDS.
+constexpr int lk5_reused(int half) { return half == 0 ? 3 : 2; }      // couples (t, t + 5) of the half; its other pairs have no partner
+constexpr int lk5_deal(int half, int j) {
+  return half == 0 ? (j < 6 ? (j >> 1) + 5 * (j & 1) : 10)             // {0,5, 1,6, 2,7, 10}
+                   : (j < 4 ? 3 + (j >> 1) + 5 * (j & 1) : 7 + j);     // {3,8, 4,9, 11, 12, 13}
+}
+
 template <int DT>
 __global__ __launch_bounds__(256) void lk5_wgrad_kernel(const srk_wgrad_args a, int tilesX, int tilesY, int tq, int trem,
                                                         unsigned x_bytes, unsigned dy_bytes) {
@@ -1252,28 +1261,36 @@ __global__ __launch_bounds__(256) void lk5_wgrad_kernel(const srk_wgrad_args a, 
     dconst[j] = (((iy - 2) * W + (ix - 2)) * a.dy_pitch + a.dy_coff + c * 8) * 2;
     dyx[j] = i < 2 * DP * DP ? (((iy - 2) & 0xffff) | ((ix - 2) << 16)) : (int)0x7fff7fff;      // never inside
   }
-  auto dma_tile = [&](int tile, int b) {
+  // a tile's DMA is 12 pieces per wave (8 of x, up to 4 of the gradient halo); piece p of tile `t` into buffer b
+  struct TileAt { int y0, x0, xbase, dbase; };
+  auto tile_at = [&](int tile) {
     int pt = tile;
     const int tX = pt % tilesX;
     pt /= tilesX;
     const int tY = pt % tilesY;
     const int n = pt / tilesY;
     const int y0 = tY * 16, x0 = tX * 16;
-    const int xbase = ((n * H + y0) * W + x0) * a.x_pitch * 2, dbase = ((n * H + y0) * W + x0) * a.dy_pitch * 2;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const bool ok = y0 + (xyx[k] & 255) < H && x0 + (xyx[k] >> 8) < W;
-      dma16_hidden(xrs, ok ? (unsigned)(xbase + xconst[k]) : 0x80000000u,
+    return TileAt{y0, x0, ((n * H + y0) * W + x0) * a.x_pitch * 2, ((n * H + y0) * W + x0) * a.dy_pitch * 2};
+  };
+  auto dma_piece = [&](const TileAt& t, int b, int p) {
+    if (p < 8) {
+      const int k = p;
+      const bool ok = t.y0 + (xyx[k] & 255) < H && t.x0 + (xyx[k] >> 8) < W;
+      dma16_hidden(xrs, ok ? (unsigned)(t.xbase + xconst[k]) : 0x80000000u,
                    (unsigned)__builtin_amdgcn_readfirstlane((int)(lds0 + b * BUF + ((k * 256 + wave * 64) << 4))));
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      if (j * 256 + wave * 64 >= 2 * DP * DP) continue;        // wave-uniform: nothing of this piece row is inside the halo image
-      const int gy = y0 + (int)(short)(dyx[j] & 0xffff), gx = x0 + (dyx[j] >> 16);
+    } else {
+      const int j = p - 8;
+      if (j * 256 + wave * 64 >= 2 * DP * DP) return;          // wave-uniform: nothing of this piece row is inside the halo image
+      const int gy = t.y0 + (int)(short)(dyx[j] & 0xffff), gx = t.x0 + (dyx[j] >> 16);
       const bool ok = (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W;
-      dma16_hidden(drs, ok ? (unsigned)(dbase + dconst[j]) : 0x80000000u,
+      dma16_hidden(drs, ok ? (unsigned)(t.dbase + dconst[j]) : 0x80000000u,
                    (unsigned)__builtin_amdgcn_readfirstlane((int)(lds0 + b * BUF + XB + ((j * 256 + wave * 64) << 4))));
     }
+  };
+  auto dma_tile = [&](int tile, int b) {
+    const TileAt t = tile_at(tile);
+#pragma unroll
+    for (int p = 0; p < 12; ++p) dma_piece(t, b, p);
   };
 
   const int rb = wave & 1, half = wave >> 1;
@@ -1282,24 +1299,11 @@ __global__ __launch_bounds__(256) void lk5_wgrad_kernel(const srk_wgrad_args a, 
   for (int j = 0; j < 7; ++j)
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc[j][e] = 0.f;
-  int aoff[2], boff[7][2];
+  int aoff[2];
 #pragma unroll
   for (int rd = 0; rd < 2; ++rd) aoff[rd] = tr_lane_off(0, rd, rb, lane);
-  {
-    const int G = lane >> 4, q = (lane & 15) >> 2, pq = lane & 3;
-#pragma unroll
-    for (int j = 0; j < 7; ++j) {
-      int fyA, fxA, fyB, fxB; bool hasB;
-      lk5_pair(half * 7 + j, fyA, fxA, fyB, fxB, hasB);
-      const int fy = (G & 1) ? fyB : fyA, fx = (G & 1) ? fxB : fxA;      // (a lone tap: its columns 16-31 repeat tap A and are not stored)
-#pragma unroll
-      for (int rd = 0; rd < 2; ++rd) {
-        const int col = 8 * (G >> 1) + 4 * rd + q;
-        boff[j][rd] = ((2 - fy) * DP + (col - fx + 2)) * 32 + pq * 8;
-      }
-    }
-  }
-  const bool do_bias = a.dbp != nullptr && wave == 2;      // wave 2's first pair is (0,0) & (1,0): its group-0 lanes see the unshifted gradient
+  // the wave of input-channel half 0 that owns pair 7 = (0,0) & (1,0): its group-0 lanes see the unshifted gradient
+  const bool do_bias = a.dbp != nullptr && wave == 0;
   float dbz = 0.f;
 
   // THREE buffers, the DMA two tiles ahead: a tile's 45 KB need 3-5k cycles to land under load, its MFMAs take 3.6k -- one tile ahead
@@ -1313,46 +1317,109 @@ __global__ __launch_bounds__(256) void lk5_wgrad_kernel(const srk_wgrad_args a, 
 #else
 #define SRK_WSTAMP(i) do { } while (0)
 #endif
-  for (int it = 0; it < nt; ++it) {
-    SRK_WSTAMP(0);
-    const char* const X = smem + (it % 3) * BUF;
-    const char* const D = X + XB;
-    // tile `it` landed (tile it + 1 may still be in flight: the younger pieces_of operations)
-    if (it + 1 < nt) { if (pieces_of == 12) asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(11)" ::: "memory"); }
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    SRK_WSTAMP(1);
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");      // ... for every wave; buffer (it + 2) % 3 (tile it - 1's) is free
-    SRK_WSTAMP(2);
-    if (it + 2 < nt) dma_tile(t0 + it + 2, (it + 2) % 3);
-    SRK_WSTAMP(3);
-    i32x4 afn, bfn[7];
-    auto fetch = [&](int y) {
-      afn = tr_read2(X + y * 2048 + aoff[0], X + y * 2048 + aoff[1]);
+  // The whole tile loop once per wave half (HALF is a compile-time constant inside: every fragment has a fixed register).
+  // Accumulators 2k / 2k + 1 (k < NR) are a pair t and its partner t + 5; the others read fresh fragments only.
+  auto tiles = [&](auto HC, auto BC) {
+    constexpr int HALF = decltype(HC)::value, NR = lk5_reused(HALF), NL = 7 - 2 * NR, NG = 1 + NR + NL;
+    constexpr bool BIAS = decltype(BC)::value;      // this wave sums the bias (half 0 only)
+    int boff[NR + NL];         // the FRESH fragments' lane offsets (first read): pairs t (k < NR), then the pairs without a partner
+    {
+      const int G = lane >> 4, q = (lane & 15) >> 2, pq = lane & 3;
 #pragma unroll
-      for (int j = 0; j < 7; ++j) bfn[j] = tr_read2(D + y * (DP * 32) + boff[j][0], D + y * (DP * 32) + boff[j][1]);
-    };
-    fetch(0);
-#pragma unroll 2
-    for (int y = 0; y < 16; ++y) {
-      const i32x4 af = afn;
-      i32x4 bf[7];
+      for (int k = 0; k < NR + NL; ++k) {
+        int fyA, fxA, fyB, fxB; bool hasB;
+        lk5_pair(lk5_deal(HALF, k < NR ? 2 * k : NR + k), fyA, fxA, fyB, fxB, hasB);
+        const int fy = (G & 1) ? fyB : fyA, fx = (G & 1) ? fxB : fxA;      // (a lone tap: its columns 16-31 repeat tap A and are not stored)
+        boff[k] = ((2 - fy) * DP + (8 * (G >> 1) + q - fx + 2)) * 32 + pq * 8;
+      }
+    }
+    for (int it = 0; it < nt; ++it) {
+      SRK_WSTAMP(0);
+      // tile `it` landed (tile it + 1 may still be in flight: the younger pieces_of operations)
+      if (it + 1 < nt) { if (pieces_of == 12) asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(11)" ::: "memory"); }
+      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      SRK_WSTAMP(1);
+      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");      // ... for every wave; buffer (it + 2) % 3 (tile it - 1's) is free
+      SRK_WSTAMP(2);
+      // tile it + 2's twelve DMA pieces go out one per row, behind the last MFMA of rows 0..11 (issued in one burst in front of
+      // the rows they cost 1.1k cycles per tile with the matrix pipe idle); all of them precede the next tile's counted wait
+      const bool more = it + 2 < nt;
+      const TileAt nx = tile_at(more ? t0 + it + 2 : t0);
+      const int nb = (it + 2) % 3;
+      SRK_WSTAMP(3);
+      // x: two slots (row y in y & 1).  Pair t of a reused couple: THREE slots, row y in (y + 3) % 3 -- pair t + 5 at row y is pair t's
+      // fragment of row y - 2, which sits in the slot that row y + 1 is fetched into, so that fetch follows the partner's MFMA.
+      // Rows -2 and -1 (the partner's rows 0 and 1) are real reads of the tile's own halo image: the line restarts at every tile.
+      i32x4 xf[2], fr[NR][3], fl[NL][2];
+      // One LDS base per fragment stream and tile, at the first row it reads; every row is then an immediate offset of its read
+      // (the bases pass through an empty asm: left to itself hipcc rebuilds buffer base + lane offset in front of every read).
+      unsigned xa[2], fa[NR + NL];
 #pragma unroll
-      for (int j = 0; j < 7; ++j) bf[j] = bfn[j];
-      if (y + 1 < 16) fetch(y + 1);
-      if (do_bias) {
-        const int qw[4] = {bf[0].x, bf[0].y, bf[0].z, bf[0].w};
+      for (int rd = 0; rd < 2; ++rd) { xa[rd] = lds0 + (unsigned)((it % 3) * BUF + aoff[rd]); asm volatile("" : "+v"(xa[rd])); }
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
+      for (int k = 0; k < NR + NL; ++k) {
+        fa[k] = lds0 + (unsigned)((it % 3) * BUF + XB + boff[k] - (k < NR ? 2 * DP * 32 : 0));
+        asm volatile("" : "+v"(fa[k]));
+      }
+      auto lds_tr2 = [](unsigned a0, unsigned a1) {
+        typedef __attribute__((address_space(3))) i16x4 lds_i16x4;
+        const i16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_i16x4*)(size_t)a0);
+        const i16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_i16x4*)(size_t)a1);
+        const i32x2 l2 = __builtin_bit_cast(i32x2, lo), h2 = __builtin_bit_cast(i32x2, hi);
+        return i32x4{l2.x, l2.y, h2.x, h2.y};
+      };
+      // (a fragment's second read is four gradient columns = 128 bytes on)
+      auto read_x = [&](int y) { xf[y & 1] = lds_tr2(xa[0] + y * 2048, xa[1] + y * 2048); };
+      auto read_r = [&](int k, int y) { fr[k][(y + 3) % 3] = lds_tr2(fa[k] + (y + 2) * (DP * 32), fa[k] + (y + 2) * (DP * 32) + 128); };
+      auto read_l = [&](int m, int y) { fl[m][y & 1] = lds_tr2(fa[NR + m] + y * (DP * 32), fa[NR + m] + y * (DP * 32) + 128); };
+      // read group g of row y, g < NG: at most two reads per MFMA gap, at most 12 a row, so a counted wait can name any of them
+      auto read_group = [&](int g, int y) {
+        if (g == 0) read_x(y);
+        else if (g <= NR) read_r(g - 1, y);
+        else read_l(g - 1 - NR, y);
+      };
+      // the bias sum: word e of pair 7's fragment of row r (= pair 2's of row r - 2), rows and words in order
+      auto bias_word = [&](int r, int e) {
+        if constexpr (BIAS) {
+          const i32x4 b7 = fr[2][(r + 1) % 3];
+          const int qw[4] = {b7.x, b7.y, b7.z, b7.w};
           float f0, f1;
           unpack2<DT>((uint32_t)qw[e], f0, f1);
-          dbz += f0 + f1;
+          float t;
+          asm("v_add_f32 %0, %1, %2" : "=v"(t) : "v"(f0), "v"(f1));       // f0 + f1, kept from becoming half of a packed add (those stall the MFMAs beside them)
+          dbz += t;
+        }
+      };
+#pragma unroll
+      for (int k = 0; k < NR; ++k) { read_r(k, -2); read_r(k, -1); }
+#pragma unroll
+      for (int g = 0; g < NG; ++g) read_group(g, 0);
+#pragma unroll
+      for (int y = 0; y < 16; ++y) {
+        const i32x4 af = xf[y & 1];
+        __builtin_amdgcn_sched_barrier(0);
+        // MFMA i of the row, then read group i of row y + 1: partners first (each frees the slot its pair's next row lands in)
+#pragma unroll
+        for (int i = 0; i < 7; ++i) {
+          if (i < NR) acc[2 * i + 1] = Tr::mma(af, fr[i][(y + 1) % 3], acc[2 * i + 1]);
+          else if (i < 2 * NR) acc[2 * (i - NR)] = Tr::mma(af, fr[i - NR][y % 3], acc[2 * (i - NR)]);
+          else acc[i] = Tr::mma(af, fl[i - 2 * NR][y & 1], acc[i]);
+          // pair 7's row y + 1 is summed during row y, one word per gap (its slot is rewritten only in row y + 1); row 0 first
+          if (BIAS) {
+            if (y == 0) { if (i < 2) { bias_word(0, 2 * i); bias_word(0, 2 * i + 1); } else if (i < 6) bias_word(1, i - 2); }
+            else if (y < 15 && i < 4) bias_word(y + 1, i);
+          }
+          if (i < NG && y + 1 < 16) read_group(i, y + 1);
+          if (i == 6 && y < 12 && more) dma_piece(nx, nb, y);
+          __builtin_amdgcn_sched_barrier(0);
         }
       }
-#pragma unroll
-      for (int j = 0; j < 7; ++j) acc[j] = Tr::mma(af, bf[j], acc[j]);
+      SRK_WSTAMP(4);
     }
-    SRK_WSTAMP(4);
-  }
+  };
+  if (do_bias) tiles(std::integral_constant<int, 0>{}, std::true_type{});
+  else if (half == 0) tiles(std::integral_constant<int, 0>{}, std::false_type{});
+  else tiles(std::integral_constant<int, 1>{}, std::false_type{});
 
   if (do_bias) {
     dbz += __shfl_xor(dbz, 32, 64);                              // the two K halves of a read
@@ -1364,7 +1431,7 @@ __global__ __launch_bounds__(256) void lk5_wgrad_kernel(const srk_wgrad_args a, 
 #pragma unroll
     for (int j = 0; j < 7; ++j) {
       int fyA, fxA, fyB, fxB; bool hasB;
-      lk5_pair(half * 7 + j, fyA, fxA, fyB, fxB, hasB);
+      lk5_pair(lk5_deal(half, j), fyA, fxA, fyB, fxB, hasB);
       if (n >= 16 && !hasB) continue;
       const int tap = n < 16 ? (fyA + 2) * 5 + fxA + 2 : (fyB + 2) * 5 + fxB + 2;
 #pragma unroll
