@@ -1033,6 +1033,11 @@ int srk_tile_place(const srk_tile_args* a, srk_stream_t stream);
 
 /* ---- misc ------------------------------------------------------------------------------------------ */
 const char* srk_last_error(void);
+/* Name of the kernel family the calling thread launched last through srk_conv2d, srk_conv2d_wgrad or srk_unfold_nchw ("" before the
+ * first): a thread-local pointer to a string literal, e.g. "conv_ws<2,4,1,1>", "conv_ws<2,4,0,0>x4" (four accumulating passes over a
+ * pixel-shuffled input), "conv_igemm<64,3>", "conv_ks", "lk5_fwd", "wgrad_atomic<3>".  The names tell apart what the dispatch tells apart;
+ * the tests assert on them which side of a dispatch decision ran. */
+const char* srk_last_kernel(void);
 int srk_version(void);
 /* number of compute units of the current device (0 when no device) */
 int srk_device_cus(void);

@@ -357,7 +357,7 @@ OTHER_SYMBOLS = ("srk_conv_tile", "srk_last_error", "srk_version", "srk_device_c
                  "srk_rmsprop_step_scaled", "srk_rmsprop_check_scaled", "srk_rmsprop_update_scaled",
                  "srk_conv_trunk", "srk_conv_trunk_ok", "srk_flip_blocks", "srk_flip_mean",
                  "srk_ms_ssim_workspace_bytes", "srk_ms_ssim_tiles", "srk_haarpsi_tiles", "srk_ssim_loss_tiles",
-                 "srk_ms_ssim_loss_workspace_bytes", "srk_ms_ssim_loss_tiles", "srk_gmsd_tiles")
+                 "srk_ms_ssim_loss_workspace_bytes", "srk_ms_ssim_loss_tiles", "srk_gmsd_tiles", "srk_last_kernel")
 
 _lib = None
 
@@ -503,6 +503,9 @@ def load():
     lib.srk_loss_scale_update.argtypes = [C.c_void_p, C.c_void_p]
     lib.srk_loss_scale_update.restype = C.c_int
     lib.srk_last_error.restype = C.c_char_p
+    if not older or not isinstance(lib.srk_last_kernel, _Absent):
+        lib.srk_last_kernel.argtypes = []
+        lib.srk_last_kernel.restype = C.c_char_p
     lib.srk_version.restype = C.c_int
     lib.srk_device_cus.restype = C.c_int
     _lib = lib

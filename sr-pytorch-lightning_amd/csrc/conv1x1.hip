@@ -229,6 +229,7 @@ int srk_conv1x1_launch(const srk_conv_args& a, hipStream_t st) {
   SRK_CHECK_ARG(nb <= 0x7fffffffLL, "srk_conv2d: %lld workgroups", nb);
   const unsigned xb = (unsigned)((long long)a.N * a.H * a.W * a.x_pitch * 2);
   const unsigned wb = (unsigned)((long long)((a.Cin + 15) / 16 * 2) * a.CoutP * 16);      // KinP / 8 chunks: later chunks read as zeros
+  srk_kernel_name = "conv1x1";
   if (a.dtype == SRK_BF16) hipLaunchKernelGGL((conv1x1_kernel<SRK_BF16>), dim3((unsigned)nb), dim3(C::NT), lds, st, a, tilesX, tilesY, ncob, PB, xb, wb);
   else hipLaunchKernelGGL((conv1x1_kernel<SRK_F16>), dim3((unsigned)nb), dim3(C::NT), lds, st, a, tilesX, tilesY, ncob, PB, xb, wb);
   SRK_LAUNCH_CHECK();

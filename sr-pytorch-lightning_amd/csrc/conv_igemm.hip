@@ -1468,10 +1468,15 @@ static bool conv_fast_ok(const srk_conv_args& a, int esz) {
   return mx * esz < 0x7fff0000LL;
 }
 
+// srk_last_kernel() name of a weight-stationary launch: "conv_ws<CBW,NKS,EARLY,EM>", and "x4" / "x9" / "xN" behind it for the r*r accumulating
+// passes over a pixel-shuffled input
+#define WS_NAME_P(s) (passes == 1 ? s : passes == 4 ? s "x4" : passes == 9 ? s "x9" : s "xN")
+#define WS_NAME_EM(s) (EM == 0 ? WS_NAME_P(s "0,0>") : EM == 1 ? WS_NAME_P(s "1,1>") : EM == 2 ? WS_NAME_P(s "1,2>") : WS_NAME_P(s "1,3>"))
+
 // one launch; `early` picks the variant that prefetches the residual / mask (see quad_compute)
 template <int DT, int CBW, int NKS, bool FAST, bool EARLY, int EM>
 static int launch_ws_one(const srk_conv_args& b, hipStream_t st, unsigned grid, int tilesX, int tilesY, int ctiles, int nptiles,
-                         unsigned xb, int tq, int trem, int xs_img, int xs_row, int xs_col, int wtap) {
+                         unsigned xb, int tq, int trem, int xs_img, int xs_row, int xs_col, int wtap, int passes) {
   typedef WsCfg C;
   constexpr int TCW = CBW * 32;
   constexpr int LDS = 9 * 2 * NKS * TCW * 16 + 2 * C::XS_BYTES + TCW * 4 + 16;      // weights, two halo buffers, bias, group-barrier counters
@@ -1481,6 +1486,8 @@ static int launch_ws_one(const srk_conv_args& b, hipStream_t st, unsigned grid, 
     srk_set_error("srk_conv2d(ws): cannot reserve %d bytes of LDS: %s", LDS, hipGetErrorString(attr));
     return (int)attr;
   }
+  static_assert((CBW == 1 && NKS == 4) || (CBW == 2 && (NKS == 4 || NKS == 1)), "name below");
+  srk_kernel_name = CBW == 1 ? WS_NAME_EM("conv_ws<1,4,") : NKS == 4 ? WS_NAME_EM("conv_ws<2,4,") : WS_NAME_EM("conv_ws<2,1,");
   hipLaunchKernelGGL((conv_ws_kernel<DT, CBW, NKS, FAST, EARLY, EM>), dim3(grid), dim3(C::NT), LDS, st, b, tilesX, tilesY, ctiles, nptiles,
                      xb, tq, trem, 0, xs_img, xs_row, xs_col, wtap);
   SRK_LAUNCH_CHECK();
@@ -1508,13 +1515,13 @@ template <int DT, int CBW, int NKS, bool FAST> int launch_ws(const srk_conv_args
   auto one = [&](const srk_conv_args& b, int xs_img, int xs_row, int xs_col, int wtap) -> int {
     if constexpr (FAST && CBW == 2) {
       if (b.mask_bits && !b.res && !b.mask)
-        return launch_ws_one<DT, CBW, NKS, FAST, true, 3>(b, st, grid, tilesX, tilesY, ctiles, (int)nptiles, xb, tq, trem, xs_img, xs_row, xs_col, wtap);
+        return launch_ws_one<DT, CBW, NKS, FAST, true, 3>(b, st, grid, tilesX, tilesY, ctiles, (int)nptiles, xb, tq, trem, xs_img, xs_row, xs_col, wtap, rin * rin);
       if (((b.res != nullptr) != (b.mask != nullptr)) && !no_early) {
-        if (b.res) return launch_ws_one<DT, CBW, NKS, FAST, true, 1>(b, st, grid, tilesX, tilesY, ctiles, (int)nptiles, xb, tq, trem, xs_img, xs_row, xs_col, wtap);
-        return launch_ws_one<DT, CBW, NKS, FAST, true, 2>(b, st, grid, tilesX, tilesY, ctiles, (int)nptiles, xb, tq, trem, xs_img, xs_row, xs_col, wtap);
+        if (b.res) return launch_ws_one<DT, CBW, NKS, FAST, true, 1>(b, st, grid, tilesX, tilesY, ctiles, (int)nptiles, xb, tq, trem, xs_img, xs_row, xs_col, wtap, rin * rin);
+        return launch_ws_one<DT, CBW, NKS, FAST, true, 2>(b, st, grid, tilesX, tilesY, ctiles, (int)nptiles, xb, tq, trem, xs_img, xs_row, xs_col, wtap, rin * rin);
       }
     }
-    return launch_ws_one<DT, CBW, NKS, FAST, false, 0>(b, st, grid, tilesX, tilesY, ctiles, (int)nptiles, xb, tq, trem, xs_img, xs_row, xs_col, wtap);
+    return launch_ws_one<DT, CBW, NKS, FAST, false, 0>(b, st, grid, tilesX, tilesY, ctiles, (int)nptiles, xb, tq, trem, xs_img, xs_row, xs_col, wtap, rin * rin);
   };
   if (rin == 1) return one(a, a.H * a.W * a.x_pitch, a.W * a.x_pitch, a.x_pitch, 2 * NKS);
   // Input stored pixel-shuffled (the dgrad of a conv + PixelShuffle(r)): channel k = (i*r+j)*64 + c lives at sub-pixel
@@ -1554,6 +1561,8 @@ template <int DT, int TC, int KS> int launch(const srk_conv_args& a, hipStream_t
     srk_set_error("srk_conv2d: bad grid %lld", nb);
     return SRK_E_BADARG;
   }
+  srk_kernel_name = TC == 128 ? (KS == 3 ? "conv_igemm<128,3>" : "conv_igemm<128,1>")
+                    : TC == 64 ? (KS == 3 ? "conv_igemm<64,3>" : "conv_igemm<64,1>") : (KS == 3 ? "conv_igemm<32,3>" : "conv_igemm<32,1>");
   hipLaunchKernelGGL((conv_igemm_kernel<DT, TC, KS>), dim3((unsigned)nb), dim3(C::NT), C::LDS_BYTES, st, a, tilesX,
                      tilesY, ctiles, (int)conv_fast_ok(a, 16 / C::CH));
   SRK_LAUNCH_CHECK();

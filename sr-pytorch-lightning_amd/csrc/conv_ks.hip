@@ -533,6 +533,7 @@ int srk_conv_ks_launch(const srk_conv_args& a, hipStream_t st) {
   const int rin = a.x_ps > 1 ? a.x_ps : 1;
   const unsigned xb = (unsigned)((long long)a.N * a.H * a.W * rin * rin * a.x_pitch * 2);
   const unsigned wb = (unsigned)(9LL * (a.Cin / 8) * a.CoutP * 16);
+  srk_kernel_name = "conv_ks";
   hipLaunchKernelGGL(fns[a.dtype == SRK_BF16 ? 0 : 1][rin > 1 ? 1 : 0], dim3((unsigned)nb), dim3(C::NT), LDS, st, a, tilesX, tilesY, ncob, xb, wb, (int)ntiles);
   SRK_LAUNCH_CHECK();
   return 0;

@@ -1490,6 +1490,9 @@ bool srk_conv_lk_ok(const srk_conv_args& a) {
   return mx * 2 < 0x7fff0000LL;
 }
 
+// srk_last_kernel() names that carry the kernel size: prefix + "5>" / "7>" / "9>"
+#define LK_NAME_K(prefix) (K == 5 ? prefix "5>" : K == 7 ? prefix "7>" : prefix "9>")
+
 template <int DT, int CPP, int NRB, int K> static int lk_launch_k(const srk_conv_args& a, hipStream_t st) {
   constexpr int XT = 16 + K - 1, XTP = (XT + 1) & ~1;
   constexpr int xs = (XT * XTP * CPP * 16 + 1023) & ~1023, slab = K * CPP * 32 * NRB * 16;
@@ -1501,6 +1504,8 @@ template <int DT, int CPP, int NRB, int K> static int lk_launch_k(const srk_conv
   const int tilesX = (a.W + 15) / 16, tilesY = (a.H + 15) / 16;
   const long long nb = (long long)a.N * tilesX * tilesY;
   SRK_CHECK_ARG(nb <= 0x7fffffffLL, "srk_conv2d: %lld workgroups", nb);
+  static_assert((CPP == 2 && NRB == 2) || (CPP == 8 && NRB == 1), "name below");
+  srk_kernel_name = CPP == 2 ? LK_NAME_K("lk_conv<2,2,") : LK_NAME_K("lk_conv<8,1,");
   hipLaunchKernelGGL((lk_conv_kernel<DT, CPP, NRB, K>), dim3((unsigned)nb), dim3(256), lds, st, a, tilesX, tilesY,
                      (unsigned)((long long)a.N * a.H * a.W * a.x_pitch * 2), (unsigned)((long long)K * slab));
   SRK_LAUNCH_CHECK();
@@ -1523,6 +1528,7 @@ template <int DT, int K> static int lk_rows_launch_k(const srk_conv_args& a, hip
   const int tilesX = (a.W + 15) / 16, tilesY = (a.H + 7) / 8;
   const long long nb = (long long)a.N * tilesX * tilesY;
   SRK_CHECK_ARG(nb <= 0x7fffffffLL, "srk_conv2d: %lld workgroups", nb);
+  srk_kernel_name = LK_NAME_K("lk_conv_rows<");
   hipLaunchKernelGGL((lk_conv_rows_kernel<DT, K>), dim3((unsigned)nb), dim3(256), lds, st, a, tilesX, tilesY,
                      (unsigned)((long long)a.N * a.H * a.W * a.x_pitch * 2), (unsigned)((long long)K * K * 64 * a.CoutP * 2));
   SRK_LAUNCH_CHECK();
@@ -1553,6 +1559,7 @@ template <int DT, int NW> static int lk5_rows_fwd_launch_w(const srk_conv_args& 
   const long long units = (long long)a.N * nb * segs;
   SRK_CHECK_ARG(units <= 0x7fffffffLL, "srk_conv2d: %lld units", units);
   const int grid = (int)(units < cus ? units : cus);
+  srk_kernel_name = "lk5_rows_fwd";
   hipLaunchKernelGGL((lk5_rows_fwd_kernel<DT, NW>), dim3(grid), dim3(NW * 64), lds, st, a, nb, segs, seg_rows, (int)units,
                      (unsigned)((long long)a.N * a.H * a.W * a.x_pitch * 2));
   SRK_LAUNCH_CHECK();
@@ -1580,6 +1587,7 @@ template <int DT> static int lk5_dgrad_launch(const srk_conv_args& a, hipStream_
   const long long units = (long long)a.N * nb * segs;
   SRK_CHECK_ARG(units <= 0x7fffffffLL, "srk_conv2d: %lld units", units);
   const int grid = (int)(units < cus ? units : cus);
+  srk_kernel_name = "lk5_dgrad";
   hipLaunchKernelGGL((lk5_dgrad_kernel<DT>), dim3(grid), dim3(256), lds, st, a, nb, segs, seg_rows, (int)units,
                      (unsigned)((long long)a.N * a.H * a.W * a.x_pitch * 2));
   SRK_LAUNCH_CHECK();
@@ -1595,6 +1603,7 @@ template <int DT> static int lk5_fwd_launch(const srk_conv_args& a, hipStream_t 
   const long long ntiles = (long long)a.N * tilesX * tilesY;
   SRK_CHECK_ARG(ntiles <= 0x7fffffffLL, "srk_conv2d: %lld tiles", ntiles);
   const int slots = (int)(ntiles < cus ? ntiles : cus);
+  srk_kernel_name = "lk5_fwd";
   hipLaunchKernelGGL((lk5_fwd_kernel<DT>), dim3(slots), dim3(256), lds, st, a, tilesX, tilesY, (int)(ntiles / slots), (int)(ntiles % slots),
                      (unsigned)((long long)a.N * a.H * a.W * a.x_pitch * 2));
   SRK_LAUNCH_CHECK();
@@ -1642,6 +1651,7 @@ template <int DT, int K> static int lk_wgrad_launch_k(const srk_wgrad_args& a, h
     if (aattr != hipSuccess) { srk_set_error("srk_conv2d_wgrad: cannot reserve LDS"); return (int)aattr; }
     const int tY8 = (a.H + LK_TR - 1) / LK_TR;
     const long long nt8 = (long long)a.N * tY8 * tilesX;
+    srk_kernel_name = LK_NAME_K("lk_wgrad_allrows<");
     hipLaunchKernelGGL((lk_wgrad_allrows_kernel<DT, K>), dim3(slabs), dim3(256), alds, st, a, tilesX, tY8, (int)nt8, (int)(nt8 / slabs), (int)(nt8 % slabs), xb, db);
     SRK_LAUNCH_CHECK();
     return 0;
@@ -1651,6 +1661,7 @@ template <int DT, int K> static int lk_wgrad_launch_k(const srk_wgrad_args& a, h
       constexpr int l5 = 3 * (16 * 16 * 128 + 13 * 1024);
       static const hipError_t a5 = hipFuncSetAttribute(reinterpret_cast<const void*>(&lk5_wgrad_kernel<DT>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
       if (a5 != hipSuccess) { srk_set_error("srk_conv2d_wgrad: cannot reserve LDS"); return (int)a5; }
+      srk_kernel_name = "lk5_wgrad";
       hipLaunchKernelGGL((lk5_wgrad_kernel<DT>), dim3(slabs), dim3(256), l5, st, a, tilesX, tilesY, (int)(ntiles / slabs), (int)(ntiles % slabs), xb, db);
       SRK_LAUNCH_CHECK();
       return 0;
@@ -1663,10 +1674,12 @@ template <int DT, int K> static int lk_wgrad_launch_k(const srk_wgrad_args& a, h
     static_assert(plds <= 160 * 1024, "LDS");
     static const hipError_t pattr = hipFuncSetAttribute(reinterpret_cast<const void*>(&lk_wgrad_packed_kernel<DT, K>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (pattr != hipSuccess) { srk_set_error("srk_conv2d_wgrad: cannot reserve LDS"); return (int)pattr; }
+    srk_kernel_name = LK_NAME_K("lk_wgrad_packed<");
     hipLaunchKernelGGL((lk_wgrad_packed_kernel<DT, K>), dim3(slabs, K), dim3(256), plds, st, a, tilesX, tilesY, (int)ntiles, (int)(ntiles / slabs), (int)(ntiles % slabs), xb, db);
     SRK_LAUNCH_CHECK();
     return 0;
   }
+  srk_kernel_name = LK_NAME_K("lk_wgrad<");
   hipLaunchKernelGGL((lk_wgrad_kernel<DT, K>), dim3(slabs, K), dim3(256), lds, st, a, tilesX, tilesY, (int)ntiles, (int)(ntiles / slabs), (int)(ntiles % slabs), xb, db);
   SRK_LAUNCH_CHECK();
   return 0;

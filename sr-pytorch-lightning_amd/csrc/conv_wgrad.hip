@@ -1009,6 +1009,7 @@ template <int DT> int launch_ws(const srk_wgrad_args& a, hipStream_t st, int sla
   const int rd = a.dy_ps > 1 ? a.dy_ps : 1;
   const unsigned xb = (unsigned)((long long)a.N * a.H * a.W * a.x_pitch * 2);
   const unsigned db = (unsigned)((long long)a.N * a.H * a.W * rd * rd * a.dy_pitch * 2);
+  srk_kernel_name = "wgrad_ws";
   hipLaunchKernelGGL((conv_wgrad_ws_kernel<DT>), dim3(slabs, cib, cob), dim3(256), LDS, st, a, tilesX, tilesY, th, xb, db,
                      (int)(ntiles / slabs), (int)(ntiles % slabs));
   SRK_LAUNCH_CHECK();
@@ -1026,6 +1027,7 @@ template <int DT, int CIB, int COB> int launch_1x1(const srk_wgrad_args& a, hipS
   const long long P = (long long)a.N * a.H * a.W;
   const long long ntiles = (P + 63) / 64;
   const int cit = (a.Cin + 64 * CIB - 1) / (64 * CIB), cot = (a.Cout + 64 * COB - 1) / (64 * COB);
+  srk_kernel_name = CIB == 2 ? "wgrad1x1_ws<2,4>" : "wgrad1x1_ws<4,2>";
   hipLaunchKernelGGL((wgrad1x1_ws_kernel<DT, CIB, COB>), dim3(slabs, cit, cot), dim3(256), LDS, st, a, (int)ntiles,
                      (unsigned)(P * a.x_pitch * 2), (unsigned)(P * a.dy_pitch * 2), (int)(ntiles / slabs), (int)(ntiles % slabs));
   SRK_LAUNCH_CHECK();
@@ -1041,6 +1043,7 @@ template <int DT> int launch_1x1_small(const srk_wgrad_args& a, hipStream_t st, 
   }
   const long long P = (long long)a.N * a.H * a.W;
   const long long ntiles = (P + 63) / 64;
+  srk_kernel_name = "wgrad1x1_small";
   hipLaunchKernelGGL((wgrad1x1_small_kernel<DT, NBUF>), dim3(slabs), dim3(256), LDS, st, a, (int)ntiles,
                      (unsigned)(P * a.x_pitch * 2), (unsigned)(P * a.dy_pitch * 2), (int)(ntiles / slabs), (int)(ntiles % slabs));
   SRK_LAUNCH_CHECK();
@@ -1072,6 +1075,7 @@ template <int DT, int KS> int launch(const srk_wgrad_args& a, hipStream_t st) {
   int slabs = 256 / (cib * cob);
   if (slabs < 1) slabs = 1;
   if (slabs > ntiles) slabs = (int)ntiles;
+  srk_kernel_name = KS == 3 ? "wgrad_atomic<3>" : "wgrad_atomic<1>";
   hipLaunchKernelGGL((conv_wgrad_kernel<DT, KS>), dim3(slabs, cib, cob), dim3(C::NT), C::LDS_BYTES, st, a, tilesX, tilesY,
                      (int)ntiles);
   SRK_LAUNCH_CHECK();

@@ -15,6 +15,8 @@ void srk_set_error(const char* fmt, ...) {
 }
 
 extern "C" const char* srk_last_error(void) { return g_err; }
+thread_local const char* srk_kernel_name = "";
+extern "C" const char* srk_last_kernel(void) { return srk_kernel_name; }
 extern "C" int srk_version(void) { return 100; }
 extern "C" int srk_device_cus(void) {
   int dev = 0;
@@ -832,12 +834,14 @@ extern "C" int srk_unfold_nchw(const srk_unfold_args* a, srk_stream_t stream) {
   if (a->Cin == 3 && a->KH == 3 && a->KW == 3 && a->Kstore == 32 && a->dtype != SRK_F32 && a->dst_pitch % 8 == 0 && a->dst_coff % 8 == 0 &&
       (reinterpret_cast<uintptr_t>(a->dst) & 15) == 0 && ((long long)a->N * a->H * a->W >= 200000 || force_px)) {
     const int gpx = grid_for((long long)a->N * a->H * a->W, 256);
+    srk_kernel_name = "unfold3x3c3";
     if (a->dtype == SRK_BF16) hipLaunchKernelGGL(unfold3x3c3_kernel<SRK_BF16>, dim3(gpx), dim3(256), 0, st, *a);
     else hipLaunchKernelGGL(unfold3x3c3_kernel<SRK_F16>, dim3(gpx), dim3(256), 0, st, *a);
     SRK_LAUNCH_CHECK();
     return 0;
   }
   const int grid = grid_for(total, 256);
+  srk_kernel_name = "unfold";
   switch (a->dtype) {
     case SRK_BF16: hipLaunchKernelGGL(unfold_kernel<SRK_BF16>, dim3(grid), dim3(256), 0, st, *a); break;
     case SRK_F16: hipLaunchKernelGGL(unfold_kernel<SRK_F16>, dim3(grid), dim3(256), 0, st, *a); break;

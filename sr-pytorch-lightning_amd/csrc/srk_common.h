@@ -25,6 +25,9 @@ static inline const char* srk_dbg_getenv(const char* name) {
   const char* d = getenv("SRK_DEBUG");
   return (d && d[0] == '1') ? getenv(name) : nullptr;
 }
+// srk_last_kernel(): the kernel family the calling thread launched last through srk_conv2d / srk_conv2d_wgrad / srk_unfold_nchw.  Every
+// launcher of those entries stores a string literal here right before its launch (one pointer store; tests assert their dispatch premise on it).
+extern thread_local const char* srk_kernel_name;
 #define SRK_CHECK_ARG(cond, ...)            \
   do {                                      \
     if (!(cond)) {                          \

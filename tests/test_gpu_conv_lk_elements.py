@@ -25,6 +25,12 @@ sys.path.insert(0, ROOT)
 from oracle import train as OT  # noqa: E402
 
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+
+import dispatch_cases as D  # noqa: E402
+
+
 pytestmark = pytest.mark.gpu
 
 
@@ -52,6 +58,18 @@ def _grads(ps, step, scale):
 # inputs (what is left is accumulation order, <= 1e-3 relative): a packing-permutation slip that touched one (kw, co) pair in 32
 # passes a relative-L2 bound of 8 %, not this one
 # ---------------------------------------------------------------------------------------------------------------
+# the kernel families (forward, data gradient, weight gradient: srk_last_kernel()) each `path` of the test below stands for
+PATH_KERNELS = {
+    "lk_wgrad_allrows / lk_conv_rows": ("lk_conv_rows<9>", "lk_conv<2,2,9>", "lk_wgrad_allrows<9>"),
+    "allrows": ("lk_conv_rows<9>", "lk_conv<2,2,9>", "lk_wgrad_allrows<9>"),
+    "lk_wgrad_packed": ("lk_conv<8,1,5>", "lk5_dgrad", "lk_wgrad_packed<5>"),
+    "allrows, 7x7": ("lk_conv_rows<7>", "lk_conv<2,2,7>", "lk_wgrad_allrows<7>"),
+    "lk_wgrad": ("lk_conv<8,1,7>", "lk_conv<2,2,7>", "lk_wgrad<7>"),
+    "lk5_wgrad": ("lk_conv<8,1,5>", "lk5_dgrad", "lk5_wgrad"),
+    "lk5_wgrad (the collapsed HR stage's shape)": ("lk_conv<8,1,5>", "lk5_dgrad", "lk5_wgrad"),
+}
+
+
 @pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("k,cout,n,h,w,path", [(9, 3, 2, 40, 33, "lk_wgrad_allrows / lk_conv_rows"), (9, 1, 1, 35, 20, "allrows"), (5, 6, 1, 33, 33, "lk_wgrad_packed"),
                                                 (7, 4, 2, 16, 47, "allrows, 7x7"), (7, 16, 2, 17, 30, "lk_wgrad"), (5, 8, 1, 21, 19, "lk5_wgrad"),
@@ -66,12 +84,15 @@ def test_large_kernel_convs_per_element_on_rounded_inputs(A, dt, k, cout, n, h, 
     gy = (torch.rand(n, cout, h, w, generator=g) * 2 - 1).to(dt)
     xd = x.permute(0, 2, 3, 1).contiguous().cuda().requires_grad_(True)
     wd, bd = wt.cuda().requires_grad_(True), b.cuda().requires_grad_(True)
-    y = ops.conv_general(xd, wd, bd, stride=1, pad=k // 2)
-    cp = y.shape[3]
-    gyd = torch.zeros(n, h, w, cp, dtype=dt)
-    gyd[..., :cout] = gy.permute(0, 2, 3, 1)
-    y.backward(gyd.cuda())
-    torch.cuda.synchronize()
+    with D.Recorder() as rec:
+        y = ops.conv_general(xd, wd, bd, stride=1, pad=k // 2)
+        cp = y.shape[3]
+        gyd = torch.zeros(n, h, w, cp, dtype=dt)
+        gyd[..., :cout] = gy.permute(0, 2, 3, 1)
+        y.backward(gyd.cuda())
+        torch.cuda.synchronize()
+    # the premise: the kernels `path` names are the ones that ran (forward, data gradient; weight gradient)
+    assert (*D._names(rec.log, "srk_conv2d"), *D._names(rec.log, "srk_conv2d_wgrad")) == PATH_KERNELS[path], (path, rec.log)
     x64, w64, b64 = x.double().requires_grad_(True), wt.double().requires_grad_(True), b.double().requires_grad_(True)
     ref = F.conv2d(x64, w64, b64, padding=k // 2)
     ref.backward(gy.double())
@@ -94,19 +115,29 @@ def test_collapsed_stage_forward_kernel_per_element(A, dt, O, n, h, w):
     """lk5_rows_fwd_kernel ((kernel column, channel) pairs on the MFMA rows, weights in registers, column taps summed through a per-wave
     scratch; O = 4: the tap-per-MFMA kernel) against float64 conv2d + pixel_shuffle on the SAME 16-bit inputs: the image is stored in
     fp32, so what is left is the order of fp32 sums -- a slip in the row / column bookkeeping (band edges, row segments, the ring) is O(1)."""
-    import torch.nn.functional as F
-    from sr_amd import ops, _lib as L
-    g = torch.Generator().manual_seed(5 + O + h + w)
-    x = (torch.rand(n, 64, h, w, generator=g) * 2 - 1).to(dt)
-    wt = (((torch.rand(4 * O, 64, 5, 5, generator=g) * 2 - 1) / np.sqrt(64 * 25)).to(dt)).float()
-    b = (torch.rand(4 * O, generator=g) * 2 - 1) * 0.1
-    post = torch.rand(O, generator=g)
-    xd = x.permute(0, 2, 3, 1).contiguous().cuda()
-    pk = ops.pack_conv(wt.cuda(), b.cuda(), dt, cache=False)
-    out = torch.full((n, O, 2 * h, 2 * w), float("nan"), device="cuda")
-    ops.conv_raw(xd, pk, N=n, H=h, W=w, Cin=64, Cout=4 * O, out=out, out_mode=L.OUT_PLANAR, ps_r=2, post_add=post.cuda())
-    torch.cuda.synchronize()
-    ref = F.pixel_shuffle(F.conv2d(x.double(), wt.double(), b.double(), padding=2), 2) + post.double().view(1, O, 1, 1)
-    got = out.cpu().double()
+    got, ins = D.collapsed_fwd_one(dt, O, n, h, w)          # (the launch and the reference are shared with test_gpu_dispatch_sides.py)
+    ref = D.collapsed_ref(*ins)
     assert bool(torch.isfinite(got).all()), "pixels the kernel never wrote"
     assert float((got - ref).abs().max()) <= 2e-5 * float(ref.abs().max())
+
+
+@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])
+def test_collapsed_stage_forward_walks_more_tiles_than_workgroups(A, dt):
+    """lk5_fwd_kernel (4-colour images, no knob) is persistent: min(ntiles, CUs) workgroups, each walks ntiles // slots tiles and the first
+    ntiles % slots of them one more (lk5_fwd_launch, csrc/conv_lk.hip).  CUs // 4 + 9 images of 17 x 20 are four ragged tiles each: every
+    workgroup has a full round and the first 36 or so a second one.  Criterion of test_collapsed_stage_forward_kernel_per_element, for
+    every image on its own, so that a failure names the images of the partial round."""
+    O, h, w = 4, 17, 20
+    cus = A._lib.load().srk_device_cus()
+    n = cus // 4 + 9
+    ntiles = n * ((h + 15) // 16) * ((w + 15) // 16)
+    slots = min(ntiles, cus)                                      # the launcher's formula, restated: the premise of this test
+    assert ntiles == 4 * n and ntiles // slots >= 1 and ntiles % slots != 0, (cus, n, ntiles, slots)
+    with D.Recorder() as rec:
+        got, ins = D.collapsed_fwd_one(dt, O, n, h, w)
+    assert D._names(rec.log, "srk_conv2d") == ["lk5_fwd"], rec.log
+    ref = D.collapsed_ref(*ins)
+    assert bool(torch.isfinite(got).all()), ("pixels the kernel never wrote, images", torch.nonzero(~torch.isfinite(got).flatten(1).all(1)).flatten().tolist())
+    err = (got - ref).abs().flatten(1).max(1).values
+    bad = torch.nonzero(err > 2e-5 * float(ref.abs().max())).flatten().tolist()
+    assert not bad, (f"images {bad} of {n} ({ntiles} tiles, {slots} workgroups, the first {ntiles % slots} walk one tile more)", float(err.max()))

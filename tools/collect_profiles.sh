@@ -8,7 +8,7 @@ TAG=${1:-r6}
 REPO=${GRAFT_REPO_ROOT:-/root/repo}
 cd "$REPO"; O=gpurun_out
 python __graft_entry__.py smoke > $O/${TAG}_smoke.txt 2>&1; tail -1 $O/${TAG}_smoke.txt
-python -m pytest tests -q -m gpu 2>&1 | tail -2 > $O/${TAG}_gpu_tests.txt; cat $O/${TAG}_gpu_tests.txt
+SRK_PROFILE_DIR=$PWD/profiles python -m pytest tests -q -m gpu 2>&1 | tail -2 > $O/${TAG}_gpu_tests.txt; cat $O/${TAG}_gpu_tests.txt      # (SRK_PROFILE_DIR: tests/test_gpu_dispatch_sides.py rewrites profiles/dispatch_sides.json, the fallback side of every dispatch decision)
 SRK_PROFILE_TAG=$TAG tools/pmc_traffic.sh 256 > /dev/null 2>&1; cp $O/${TAG}_pmc_traffic.json profiles/${TAG}_pmc_traffic.json      # (the bench line below quotes it: every configuration's dominant kernel in its step)
 python bench.py --full > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_default.err; tail -c 400 $O/${TAG}_bench_default.json; echo
 python bench.py --full --dtype f16 --no-cpu-baseline --no-other-configs > $O/${TAG}_bench_default_f16.json 2>/dev/null
