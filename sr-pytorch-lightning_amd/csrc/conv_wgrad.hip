@@ -434,9 +434,22 @@ SRK_DEV void wgrad_ws_body16(const srk_wgrad_args& a, const int slot, const int 
 // pieces so that EVERY lane issues the same 10 pieces per tile: out-of-image and past-the-end pieces use out-of-range offsets), four of them fill the 160 KB,
 // and the wait in front of a tile is the constant vmcnt(2 x 10): the two younger tiles stay in flight.  Same MFMAs per pixel; the halo rows cost 10 / 8
 // instead of 18 / 16 of X.  The slabs differ from the 16-row form in summation order only (a tile row is still one K step).
+//
+// The seam between two tiles holds nothing but MFMAs (profiles/wgrad_ws_tile_boundary.txt).  Before, every wave ran between a tile's barrier and its first
+// MFMA, with the matrix pipe empty: the bias-gradient block (4 LDS reads, each waited for, 32 conversions, 16 packed adds), ~50 dependent scalar instructions
+// of two integer divisions for the tile three ahead, and the ramp of 20 fragment reads.  Now
+//  * the wait for tile it + 1, the barrier and the reads of tile it + 1's first fragments (halo rows 0-2, gradient row 0) sit inside the LAST row of tile it,
+//    behind its first MFMAs; the fragments travel to the next tile in registers of their own;
+//  * the bias sum of a tile reads one 16-byte word per row in rows 0-3 and converts and adds it between the MFMAs of the row after (scalar v_add_f32:
+//    the packed ones stall the MFMAs beside them), in the same order as before: k = 0..3 within a tile, tiles in order;
+//  * (tX, tY, n) of the tile three ahead advance by counters, inside row 6: one division pair per workgroup, none in the loop.
+// Same MFMAs per accumulator in the same row order, same bias adds in the same order: slabs and bias slabs are bit-identical to the earlier form.
 constexpr int WS_TH = 8;                                 // tile height of the slab-mode 3x3 weight gradient (host: tilesY = ceil(H / WS_TH))
 
-template <int DT>
+SRK_DEV void add_f32_unpacked(float& s, float v) { asm("v_add_f32_e32 %0, %0, %1" : "+v"(s) : "v"(v)); }
+
+// BIAS: this workgroup also sums dY over its tiles (the layer has a bias and this is ci block 0); uniform over the workgroup, chosen by the kernels below
+template <int DT, bool BIAS>
 SRK_DEV void wgrad_ws_body8(const srk_wgrad_args& a, const int slot, const int cib, const int cob, const int tilesX, const int tilesY,
                            const unsigned x_bytes, const unsigned dy_bytes, const int tq, const int trem, char* const smem) {
   typedef WgCfg<DT, 3> C;
@@ -492,18 +505,24 @@ SRK_DEV void wgrad_ws_body8(const srk_wgrad_args& a, const int slot, const int c
   // the MFMA loop of the previous tile (an LDS-DMA issue costs 60-100 cycles of the wave's time in front of the loop,
   // with the matrix pipe idle: one wave per SIMD; between MFMAs most of that hides behind the running MFMA)
   struct TileAddr { int y0, x0, xbase, dbase; bool colok, live; unsigned Xb; };   // Xb: LDS byte address of the buffer; live: a tile of this workgroup
-  auto tile_addr = [&](int it_, char* Xb) {
+  // The workgroup's tiles are consecutive in (n, tY, tX) order, so the position of the next tile to request advances by counters: one division pair here,
+  // none per tile.  Past the end the counters run on (at most AHEAD tiles); such a tile is not `live` and every piece of it is an out-of-range offset.
+  int nx_tX = t0 % tilesX, nx_tY = (t0 / tilesX) % tilesY, nx_n = (t0 / tilesX) / tilesY;
+  auto tile_addr = [&](int it_) {             // the tiles are asked for in order: it_ = 0, 1, 2, ...
     TileAddr t;
     t.live = it_ < nt;
-    const int pt = t0 + (t.live ? it_ : 0);
-    const int tX = pt % tilesX;
-    const int q = pt / tilesX;
-    const int tY = q % tilesY, n = q / tilesY;
-    t.y0 = tY * TH; t.x0 = tX * 16;
-    t.xbase = (((n * H + t.y0) * W + t.x0) * a.x_pitch) * ESZ;
-    t.dbase = (((n * H * rd + t.y0 * rd) * (W * rd) + t.x0 * rd) * a.dy_pitch) * ESZ;
+    t.y0 = nx_tY * TH; t.x0 = nx_tX * 16;
+    const int row = nx_n * H + t.y0;
+    t.xbase = ((row * W + t.x0) * a.x_pitch) * ESZ;
+    t.dbase = ((row * rd * (W * rd) + t.x0 * rd) * a.dy_pitch) * ESZ;
     t.colok = t.live && d_cok && (t.x0 + d_ix < W);
-    t.Xb = lds0 + (unsigned)(Xb - smem);
+    t.Xb = lds0 + (unsigned)((it_ & (NBUF - 1)) * BUF_BYTES);
+    const bool wx = nx_tX + 1 == tilesX;
+    nx_tX = wx ? 0 : nx_tX + 1;
+    nx_tY += wx ? 1 : 0;
+    const bool wy = nx_tY == tilesY;
+    nx_tY = wy ? 0 : nx_tY;
+    nx_n += wy ? 1 : 0;
     return t;
   };
   auto dma_x_piece = [&](const TileAddr& t, int k) {
@@ -517,8 +536,8 @@ SRK_DEV void wgrad_ws_body8(const srk_wgrad_args& a, const int slot, const int c
     const unsigned voff = ok ? (unsigned)(t.dbase + dconst + k * dkstride) : 0x80000000u;
     dma16_hidden(drs, voff, __builtin_amdgcn_readfirstlane(t.Xb + XS_PAD + ((k * GT + wave * 64) << 4)));
   };
-  auto dma_tile = [&](int it_, char* Xb) {
-    const TileAddr t = tile_addr(it_, Xb);
+  auto dma_tile = [&](int it_) {
+    const TileAddr t = tile_addr(it_);
 #pragma unroll
     for (int k = 0; k < NPK; ++k) dma_x_piece(t, k);
 #pragma unroll
@@ -531,7 +550,6 @@ SRK_DEV void wgrad_ws_body8(const srk_wgrad_args& a, const int slot, const int c
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc[t][e] = 0.f;
   float bsum8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  const bool do_bias = a.dbp != nullptr && cib == 0;
   int xoff[KS][2], doff[2];
 #pragma unroll
   for (int kw = 0; kw < KS; ++kw) {
@@ -540,41 +558,42 @@ SRK_DEV void wgrad_ws_body8(const srk_wgrad_args& a, const int slot, const int c
   }
   doff[0] = tr_lane_off(0, 0, cbk, lane);
   doff[1] = tr_lane_off(0, 1, cbk, lane);
-
-#pragma unroll
-  for (int k = 0; k < AHEAD; ++k) dma_tile(k, smem + k * BUF_BYTES);      // tiles 0 .. 2 (past-the-end ones as out-of-range pieces)
-#pragma unroll 1
-  for (int it = 0; it < nt; ++it) {
-    char* const Xs = smem + (it & (NBUF - 1)) * BUF_BYTES;
-    char* const Ds = Xs + XS_PAD;
-    asm volatile("s_waitcnt vmcnt(%0)" :: "n"((AHEAD - 1) * PPT) : "memory");     // tile `it` landed; the two younger tiles stay in flight
-    __builtin_amdgcn_s_barrier();                         // ... for every wave; the buffer of tile it - 1 is free
-    constexpr bool more = true;                           // (a tile is ALWAYS requested: past the end as out-of-range pieces)
-    const TileAddr nxt = tile_addr(it + AHEAD, smem + ((it + AHEAD) & (NBUF - 1)) * BUF_BYTES);
-
-    if (do_bias) {
-      // bias gradient: lane owns LDS slot (tid&7) of pixels (tid>>3) + 32k; the slot's channel chunk is the same
-      // for all 8 of them (the swizzle depends on the column, and 32 pixels = 2 full rows)
-#pragma unroll
-      for (int k = 0; k < NDK; ++k) {
-        const i32x4 raw = lds_read16(Ds + ((tid + 256 * k) << 4));
-        const uint32_t w4[4] = {(uint32_t)raw.x, (uint32_t)raw.y, (uint32_t)raw.z, (uint32_t)raw.w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          bsum8[2 * i] += Tr::to_f32((uint16_t)(w4[i] & 0xffff));
-          bsum8[2 * i + 1] += Tr::to_f32((uint16_t)(w4[i] >> 16));
-        }
-      }
-    }
-    // K loop over the 16 tile rows; the fragments of step y+1 (one new halo row, one dY row) are fetched while
-    // the 9 MFMAs of step y run (4 rotating halo-row slots), sched_barrier keeps the groups apart
-    i32x4 xf[4][KS];
+  // a tile's first fragments: halo rows 0-2 (3 taps each) and gradient row 0, 20 transposing reads
+  i32x4 pxf[3][KS], pbf;
+  auto read_first_frags = [&](const char* Xb) {
+    const char* const Db = Xb + XS_PAD;
+    pbf = tr_read2(Db + doff[0], Db + doff[1]);
 #pragma unroll
     for (int rr = 0; rr < 3; ++rr)
 #pragma unroll
       for (int kw = 0; kw < KS; ++kw)
-        xf[rr][kw] = tr_read2(Xs + xoff[kw][0] + rr * (C::PITCH * 128), Xs + xoff[kw][1] + rr * (C::PITCH * 128));
-    i32x4 bf = tr_read2(Ds + doff[0], Ds + doff[1]);
+        pxf[rr][kw] = tr_read2(Xb + xoff[kw][0] + rr * (C::PITCH * 128), Xb + xoff[kw][1] + rr * (C::PITCH * 128));
+  };
+
+#pragma unroll
+  for (int k = 0; k < AHEAD; ++k) dma_tile(k);            // tiles 0 .. 2 (past-the-end ones as out-of-range pieces)
+  TileAddr nxt = tile_addr(AHEAD);                        // the tile requested during tile 0
+  asm volatile("s_waitcnt vmcnt(%0)" :: "n"((AHEAD - 1) * PPT) : "memory");     // tile 0 landed; the two younger tiles stay in flight
+  __builtin_amdgcn_s_barrier();                           // ... for every wave
+  read_first_frags(smem);
+#pragma unroll 1
+  for (int it = 0; it < nt; ++it) {
+    const char* const Xs = smem + (it & (NBUF - 1)) * BUF_BYTES;
+    const char* const Ds = Xs + XS_PAD;
+    const char* const Xn = smem + ((it + 1) & (NBUF - 1)) * BUF_BYTES;      // tile it + 1 (past the end: a zero-filled buffer, read and never used)
+    // K loop over the 8 tile rows; the fragments of step y+1 (one new halo row, one dY row) are fetched while
+    // the 9 MFMAs of step y run (4 rotating halo-row slots), sched_barrier keeps the groups apart.  Rows 0-2 and the
+    // gradient row 0 came in registers from the seam inside the previous tile's last row.
+    i32x4 xf[4][KS];
+#pragma unroll
+    for (int rr = 0; rr < 3; ++rr)
+#pragma unroll
+      for (int kw = 0; kw < KS; ++kw) xf[rr][kw] = pxf[rr][kw];
+    i32x4 bf = pbf;
+    // bias gradient: lane owns LDS slot (tid&7) of pixels (tid>>3) + 32k; the slot's channel chunk is the same
+    // for all 4 of them (the swizzle depends on the column, and 32 pixels = 2 full rows).  Word k is read in row k and added in row k + 1.
+    i32x4 braw = {0, 0, 0, 0};
+    TileAddr nn = nxt;
 #pragma unroll
     for (int y = 0; y < TH; ++y) {
       i32x4 bfn = bf;
@@ -585,18 +604,43 @@ SRK_DEV void wgrad_ws_body8(const srk_wgrad_args& a, const int slot, const int c
           xf[nr & 3][kw] = tr_read2(Xs + xoff[kw][0] + nr * (C::PITCH * 128), Xs + xoff[kw][1] + nr * (C::PITCH * 128));
         bfn = tr_read2(Ds + doff[0] + (y + 1) * (16 * 128), Ds + doff[1] + (y + 1) * (16 * 128));
       }
+      const i32x4 bprev = braw;
+      if (BIAS && y < NDK) braw = lds_read16(Ds + ((tid + 256 * y) << 4));
 #pragma unroll
       for (int t = 0; t < 9; ++t) {
         const int kh = t / KS, kw = t - kh * KS;
         acc[t] = Tr::mma(xf[(y + kh) & 3][kw], bf, acc[t]);
-        // next tile's DMA, front-loaded (3 pieces per step in steps 0-5, the rest by step 7): a piece takes 3-5k cycles
-        // to land under load and the whole tile must be there when this loop (5.3k cycles) ends
-        if (t == 1 && y < NPK && more) dma_x_piece(nxt, y);
-        if (t == 5 && y < NDK && more) dma_d_piece(nxt, y);
+        // the DMA of tile it + 3, front-loaded (one halo piece per row in rows 0-5, one gradient piece in rows 0-3): a piece takes 3-5k cycles
+        // to land under load
+        if (t == 1 && y < NPK) dma_x_piece(nxt, y);
+        if (t == 5 && y < NDK) dma_d_piece(nxt, y);
+        if (BIAS && y >= 1 && y <= NDK && t >= 2 && t != 5 && t <= 6) {
+          const int i = t - 2 - (t > 5 ? 1 : 0);         // t = 2, 3, 4, 6: 32-bit word i of the 16-byte word read in row y - 1
+          const uint32_t w = (uint32_t)bprev[i];
+          add_f32_unpacked(bsum8[2 * i], Tr::to_f32((uint16_t)(w & 0xffff)));
+          add_f32_unpacked(bsum8[2 * i + 1], Tr::to_f32((uint16_t)(w >> 16)));
+        }
+        if (y == TH - 2 && t == 3) nn = tile_addr(it + 1 + AHEAD);       // position of the tile the NEXT tile requests: scalar work beside MFMAs
+        if (y == TH - 1 && t == 0) {
+          // ---- the seam.  This row's fragments were requested in row 6: with lgkmcnt(0) this wave has finished reading tile `it`'s buffer.
+          // Tile it + 3's ten pieces went out in rows 0-5 of this tile and nothing since, so exactly the two younger tiles (it + 2, it + 3) may
+          // stay in flight: vmcnt((AHEAD - 1) * PPT) means this wave's pieces of tile it + 1 landed.  After the barrier that holds for every
+          // wave, and every wave has all of tile `it` in registers: its buffer is free for the DMA of tile it + 4, which starts in row 0 of
+          // tile it + 1.  One MFMA is in the pipe in front of the barrier and one behind it; the other seven of the row cover the 20 reads.
+          __builtin_amdgcn_sched_barrier(0);
+          asm volatile("s_waitcnt lgkmcnt(0)\n\ts_waitcnt vmcnt(%0)" :: "n"((AHEAD - 1) * PPT) : "memory");
+          __builtin_amdgcn_s_barrier();
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        if (y == TH - 1 && t == 1) {                      // (one more MFMA goes into the pipe before the reads: none of them stands between the barrier and an MFMA)
+          __builtin_amdgcn_sched_barrier(0);
+          read_first_frags(Xn);
+        }
       }
       bf = bfn;
       __builtin_amdgcn_sched_barrier(0);
     }
+    nxt = nn;
   }
 
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // the past-the-end pieces (zero fill) are LDS writes too: done before the buffers are reused
@@ -620,7 +664,7 @@ SRK_DEV void wgrad_ws_body8(const srk_wgrad_args& a, const int slot, const int c
       }
     }
   }
-  if (do_bias) {
+  if (BIAS) {
     // fixed-order reduction of the per-lane chunk sums: channel c lives in chunk c>>3, held by the 32 lanes
     // (hi, q16) with slot (c>>3) ^ swz(q16)
     float* const bred = reinterpret_cast<float*>(smem);      // [256][8]
@@ -638,12 +682,20 @@ SRK_DEV void wgrad_ws_body8(const srk_wgrad_args& a, const int slot, const int c
   }
 }
 
+// the 8-row body with or without the bias sum: one uniform branch per workgroup instead of one per tile
+template <int DT>
+SRK_DEV void wgrad_ws_run8(const srk_wgrad_args& a, const int slot, const int cib, const int cob, const int tilesX, const int tilesY,
+                          const unsigned x_bytes, const unsigned dy_bytes, const int tq, const int trem, char* const smem) {
+  if (a.dbp != nullptr && cib == 0) wgrad_ws_body8<DT, true>(a, slot, cib, cob, tilesX, tilesY, x_bytes, dy_bytes, tq, trem, smem);
+  else wgrad_ws_body8<DT, false>(a, slot, cib, cob, tilesX, tilesY, x_bytes, dy_bytes, tq, trem, smem);
+}
+
 template <int DT>
 __global__ __launch_bounds__(256, 1) void conv_wgrad_ws_kernel(const srk_wgrad_args a, int tilesX, int tilesY, int th,
                                                                 unsigned x_bytes, unsigned dy_bytes, int tq, int trem) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   // th: tile height the host cut the images with (ws_tile_height: 8 = the four-buffer ring, 16 = two buffers); uniform over the launch
-  if (th == WS_TH) wgrad_ws_body8<DT>(a, blockIdx.x, blockIdx.y, blockIdx.z, tilesX, tilesY, x_bytes, dy_bytes, tq, trem, smem);
+  if (th == WS_TH) wgrad_ws_run8<DT>(a, blockIdx.x, blockIdx.y, blockIdx.z, tilesX, tilesY, x_bytes, dy_bytes, tq, trem, smem);
   else wgrad_ws_body16<DT>(a, blockIdx.x, blockIdx.y, blockIdx.z, tilesX, tilesY, x_bytes, dy_bytes, tq, trem, smem);
 }
 
@@ -683,7 +735,7 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_ws_group_kernel(const WgJob
   const int per = j.ncib * j.ncob;
   const int slot = local / per, rem = local - slot * per;
   const int cib = rem / j.ncob, cob = rem - cib * j.ncob;
-  if (j.th == WS_TH) wgrad_ws_body8<DT>(j.a, slot, cib, cob, j.tilesX, j.tilesY, j.x_bytes, j.dy_bytes, j.tq, j.trem, smem);
+  if (j.th == WS_TH) wgrad_ws_run8<DT>(j.a, slot, cib, cob, j.tilesX, j.tilesY, j.x_bytes, j.dy_bytes, j.tq, j.trem, smem);
   else wgrad_ws_body16<DT>(j.a, slot, cib, cob, j.tilesX, j.tilesY, j.x_bytes, j.dy_bytes, j.tq, j.trem, smem);
 }
 
