@@ -13,6 +13,7 @@
 //
 // Replaces: autograd's conv2d weight/bias gradient for models/common.py:7-30 convs.
 #include <stdlib.h>
+#include <mutex>
 #include "srk_common.h"
 
 namespace {
@@ -435,121 +436,197 @@ SRK_DEV void wgrad_ws_body16(const srk_wgrad_args& a, const int slot, const int 
 // and the wait in front of a tile is the constant vmcnt(2 x 10): the two younger tiles stay in flight.  Same MFMAs per pixel; the halo rows cost 10 / 8
 // instead of 18 / 16 of X.  The slabs differ from the 16-row form in summation order only (a tile row is still one K step).
 //
-// The seam between two tiles holds nothing but MFMAs (profiles/wgrad_ws_tile_boundary.txt).  Before, every wave ran between a tile's barrier and its first
-// MFMA, with the matrix pipe empty: the bias-gradient block (4 LDS reads, each waited for, 32 conversions, 16 packed adds), ~50 dependent scalar instructions
-// of two integer divisions for the tile three ahead, and the ramp of 20 fragment reads.  Now
-//  * the wait for tile it + 1, the barrier and the reads of tile it + 1's first fragments (halo rows 0-2, gradient row 0) sit inside the LAST row of tile it,
-//    behind its first MFMAs; the fragments travel to the next tile in registers of their own;
-//  * the bias sum of a tile reads one 16-byte word per row in rows 0-3 and converts and adds it between the MFMAs of the row after (scalar v_add_f32:
-//    the packed ones stall the MFMAs beside them), in the same order as before: k = 0..3 within a tile, tiles in order;
-//  * (tX, tY, n) of the tile three ahead advance by counters, inside row 6: one division pair per workgroup, none in the loop.
-// Same MFMAs per accumulator in the same row order, same bias adds in the same order: slabs and bias slabs are bit-identical to the earlier form.
+// The seam between two tiles holds nothing but MFMAs (profiles/wgrad_ws_tile_boundary.txt): the barrier and the reads of tile it + 1's first fragments (halo
+// rows 0-2, gradient row 0) sit inside the LAST row of tile it, behind its first MFMAs, and the fragments travel to the next tile in registers of their own.
+// The DMA of the tile three ahead, the tile position (counters: one division pair per workgroup, none in the loop) and the bias sum (one 16-byte word per
+// lane and gradient-row pair, scalar v_add_f32: the packed ones stall the MFMAs beside them; k = 0..3 within a tile, tiles in order) belong
+// to the helper waves below.
 constexpr int WS_TH = 8;                                 // tile height of the slab-mode 3x3 weight gradient (host: tilesY = ceil(H / WS_TH))
 
 SRK_DEV void add_f32_unpacked(float& s, float v) { asm("v_add_f32_e32 %0, %0, %1" : "+v"(s) : "v"(v)); }
 
+// Helper waves.  The 8-row form runs as 512 threads, two waves per SIMD: waves 0-3 compute, waves 4-7 help (wave 4 + w shares a SIMD with wave w).  A
+// compute wave alone on its SIMD issued, inside its MFMA stream, ten LDS-DMA pieces per tile (address VALU, the M0 write, the buffer load) and, in
+// workgroups that sum the bias, 4 LDS reads, 32 conversions and 32 adds: hundreds of cycles per tile in which that SIMD's matrix pipe had nothing queued
+// (an in-order wave).  Now helper wave hw = wave - 4 owns exactly what compute wave hw issued: the same per-lane constants (from tid - 256), the same ten
+// pieces per tile to the same LDS addresses, past-the-end tiles still as out-of-range pieces, and the same bias words in the same order.  A compute wave
+// is left with the fragment reads, the 72 MFMAs and one barrier per tile.
+//   helper, tile it : [B(it-1)]  the pieces of tile it + 3 (its buffer held tile it - 1: free since B(it-1)); the bias words of tile it;
+//                     s_waitcnt lgkmcnt(0) vmcnt(2 x 10): this wave's pieces of tile it + 1 landed;  [B(it)]
+//   compute, tile it: [B(it-1)]  rows 0-6, row 7's first MFMA; s_waitcnt lgkmcnt(0): done with tile it's buffer;  [B(it)]  tile it + 1's first fragments
+// Another wave's DMA is visible through the issuer's vmcnt plus a barrier, so a compute wave needs no vmcnt: it has no loads in flight inside the loop.
+// BARRIERS per wave, either role: 1 (prologue: tile 0 landed) + nt (one per tile) + 2 (the bias reduction, BIAS workgroups only) -- a function of nt and
+// BIAS alone, both uniform over the workgroup.  Counted in the generated ISA of every instantiation: 4 s_barrier in the helper branch (prologue, loop,
+// reduction x 2), 4 in the compute branch (prologue, seam, reduction x 2) with BIAS, 2 + 2 without.
+// Same bytes in LDS, same MFMAs per accumulator in the same order, same bias adds in the same order: slabs and bias slabs are bit-identical to the
+// one-wave-per-SIMD form.  215 registers per lane (the accumulators included), no vector spills: two waves per SIMD (profiles/wgrad_helper_waves.txt).
+#ifndef SRK_WG_STAMPS
+#define SRK_WG_STAMPS 0                                  // diagnostics build (make stamp, tools/stamp_wg.py): per-tile stamps of waves 0 and 4
+#endif
+// A/B builds (profiles/wgrad_helper_waves.txt): s_sleep of this many x 64 cycles behind every piece instead of one burst; s_setprio of the compute waves
+#ifndef SRK_WG_HELPER_SLEEP
+#define SRK_WG_HELPER_SLEEP 0
+#endif
+#ifndef SRK_WG_COMPUTE_PRIO
+#define SRK_WG_COMPUTE_PRIO 0
+#endif
+constexpr int WS8_THREADS = 512;
+
 // BIAS: this workgroup also sums dY over its tiles (the layer has a bias and this is ci block 0); uniform over the workgroup, chosen by the kernels below
 template <int DT, bool BIAS>
 SRK_DEV void wgrad_ws_body8(const srk_wgrad_args& a, const int slot, const int cib, const int cob, const int tilesX, const int tilesY,
-                           const unsigned x_bytes, const unsigned dy_bytes, const int tq, const int trem, char* const smem) {
+                           const unsigned x_bytes, const unsigned dy_bytes, const int tq, const int trem, char* const smem, const bool single) {
   typedef WgCfg<DT, 3> C;
   typedef typename C::Tr Tr;
-  typedef typename Tr::elem elem;
   constexpr int CH = C::CH, KS = 3, GT = 256, ESZ = C::ESZ;
   constexpr int TH = WS_TH, NBUF = 4, AHEAD = NBUF - 1;
   constexpr int XPIECES = (TH + 2) * C::TIN * 8;       // 16-byte pieces of the halo image: (TH + 2) rows x 18 columns x 8 chunks
   constexpr int NPK = (XPIECES + GT - 1) / GT;         // 6 halo pieces per lane (the image is padded to NPK * GT pieces)
   constexpr int NDK = TH * 16 * 8 / GT;                // 4 dY pieces per lane
-  constexpr int PPT = NPK + NDK;                       // vector-memory operations per lane and tile: ALWAYS issued (the counted waits rely on it)
+  constexpr int PPT = NPK + NDK;                       // vector-memory operations per helper lane and tile: ALWAYS issued (the counted waits rely on it)
   constexpr int XS_PAD = NPK * GT * 16, DYS = TH * 16 * 128;
   constexpr int BUF_BYTES = XS_PAD + DYS;
   static_assert(NBUF * BUF_BYTES <= 160 * 1024, "the ring must fit the LDS");
 
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int rb = wave >> 1, cbk = wave & 1;
-  const int H = a.H, W = a.W;
-  const int nch_x = a.Cin / CH, nch_d = a.Cout / CH;
-
+  const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
   const int t0 = slot * tq + min(slot, trem);
   const int nt = tq + (slot < trem ? 1 : 0);
+#if SRK_WG_STAMPS
+  // behind the bias slabs of a SINGLE launch (tools/stamp_wg.py sizes the scratch for it; grouped launches write no stamps): [wave 0 | wave 4][32 tiles]
+  // [top of the tile | in front of the tile's barrier]
+  unsigned long long* const stamp = (single && slot == 0 && cib == 0 && cob == 0 && (threadIdx.x & 255) == 0 && a.dbp)
+                                        ? reinterpret_cast<unsigned long long*>(a.dbp + (size_t)a.nslabs * a.Cout) + (wave >> 2) * 64 : nullptr;
+#define SRK_GSTAMP(i) do { if (stamp && it < 32) stamp[it * 2 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
+#else
+#define SRK_GSTAMP(i) do { } while (0)
+#endif
 
-  // ---- per-lane DMA constants --------------------------------------------------------------------------
-  const i32x4 xrs = make_rsrc4(a.x, x_bytes), drs = make_rsrc4(a.dy, dy_bytes);
-  const unsigned lds0 = lds_addr_of(smem);
-  int pconst[NPK], pyx[NPK];
+  if (wave >= 4) {
+    // =============================== helper wave: the tile DMA and the bias sum ===============================
+    const int tid = (int)threadIdx.x - GT, hw = wave - 4;
+    const int H = a.H, W = a.W;
+    const int nch_x = a.Cin / CH, nch_d = a.Cout / CH;
+    // ---- per-lane DMA constants --------------------------------------------------------------------------
+    const i32x4 xrs = make_rsrc4(a.x, x_bytes), drs = make_rsrc4(a.dy, dy_bytes);
+    const unsigned lds0 = lds_addr_of(smem);
+    int pconst[NPK], pyx[NPK];
 #pragma unroll
-  for (int k = 0; k < NPK; ++k) {
-    const int i = tid + k * GT;
-    const int sl = i & 7, p = i >> 3;
-    const int iy = p / C::TIN, ix = p - iy * C::TIN;
-    const int c = cib * 8 + (sl ^ swz(ix));
-    pconst[k] = (((iy - 1) * W + (ix - 1)) * a.x_pitch + a.x_coff + c * CH) * ESZ;
-    pyx[k] = (i < XPIECES && c < nch_x) ? (((iy - 1) & 0xffff) | ((ix - 1) << 16)) : (int)0x7fff7fff;      // (padding pieces: never inside the image)
-  }
-  // dY piece i = tid + 256k: slot, column and channel chunk do not depend on k, the row advances by 2 per k
-  const int rd = a.dy_ps > 1 ? a.dy_ps : 1;
-  const int d_ix = (tid >> 3) & 15, d_iy0 = tid >> 7;
-  const int d_c = cob * 8 + ((tid & 7) ^ swz(d_ix));
-  const bool d_cok = d_c < nch_d;
-  int dconst, dkstride;
-  {
-    const int Csd = a.Cout / (rd * rd);
-    const int k0 = d_c * CH;
-    const int ij = k0 / Csd, c0 = k0 - ij * Csd;
-    const int si = ij / rd, sj = ij - si * rd;
-    dconst = (((d_iy0 * rd + si) * (W * rd) + d_ix * rd + sj) * a.dy_pitch + a.dy_coff + c0) * ESZ;
-    dkstride = 2 * rd * (W * rd) * a.dy_pitch * ESZ;
-  }
-  // one tile's DMA = 11 halo pieces + 8 dY pieces per lane.  The pieces are issued one or two per K-step from inside
-  // the MFMA loop of the previous tile (an LDS-DMA issue costs 60-100 cycles of the wave's time in front of the loop,
-  // with the matrix pipe idle: one wave per SIMD; between MFMAs most of that hides behind the running MFMA)
-  struct TileAddr { int y0, x0, xbase, dbase; bool colok, live; unsigned Xb; };   // Xb: LDS byte address of the buffer; live: a tile of this workgroup
-  // The workgroup's tiles are consecutive in (n, tY, tX) order, so the position of the next tile to request advances by counters: one division pair here,
-  // none per tile.  Past the end the counters run on (at most AHEAD tiles); such a tile is not `live` and every piece of it is an out-of-range offset.
-  int nx_tX = t0 % tilesX, nx_tY = (t0 / tilesX) % tilesY, nx_n = (t0 / tilesX) / tilesY;
-  auto tile_addr = [&](int it_) {             // the tiles are asked for in order: it_ = 0, 1, 2, ...
-    TileAddr t;
-    t.live = it_ < nt;
-    t.y0 = nx_tY * TH; t.x0 = nx_tX * 16;
-    const int row = nx_n * H + t.y0;
-    t.xbase = ((row * W + t.x0) * a.x_pitch) * ESZ;
-    t.dbase = ((row * rd * (W * rd) + t.x0 * rd) * a.dy_pitch) * ESZ;
-    t.colok = t.live && d_cok && (t.x0 + d_ix < W);
-    t.Xb = lds0 + (unsigned)((it_ & (NBUF - 1)) * BUF_BYTES);
-    const bool wx = nx_tX + 1 == tilesX;
-    nx_tX = wx ? 0 : nx_tX + 1;
-    nx_tY += wx ? 1 : 0;
-    const bool wy = nx_tY == tilesY;
-    nx_tY = wy ? 0 : nx_tY;
-    nx_n += wy ? 1 : 0;
-    return t;
-  };
-  auto dma_x_piece = [&](const TileAddr& t, int k) {
-    const int gy = t.y0 + (int)(short)(pyx[k] & 0xffff), gx = t.x0 + (pyx[k] >> 16);
-    const bool ok = t.live && (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W;
-    const unsigned voff = ok ? (unsigned)(t.xbase + pconst[k]) : 0x80000000u;
-    dma16_hidden(xrs, voff, __builtin_amdgcn_readfirstlane(t.Xb + ((k * GT + wave * 64) << 4)));
-  };
-  auto dma_d_piece = [&](const TileAddr& t, int k) {
-    const bool ok = t.colok && (t.y0 + d_iy0 + 2 * k < H);
-    const unsigned voff = ok ? (unsigned)(t.dbase + dconst + k * dkstride) : 0x80000000u;
-    dma16_hidden(drs, voff, __builtin_amdgcn_readfirstlane(t.Xb + XS_PAD + ((k * GT + wave * 64) << 4)));
-  };
-  auto dma_tile = [&](int it_) {
-    const TileAddr t = tile_addr(it_);
+    for (int k = 0; k < NPK; ++k) {
+      const int i = tid + k * GT;
+      const int sl = i & 7, p = i >> 3;
+      const int iy = p / C::TIN, ix = p - iy * C::TIN;
+      const int c = cib * 8 + (sl ^ swz(ix));
+      pconst[k] = (((iy - 1) * W + (ix - 1)) * a.x_pitch + a.x_coff + c * CH) * ESZ;
+      pyx[k] = (i < XPIECES && c < nch_x) ? (((iy - 1) & 0xffff) | ((ix - 1) << 16)) : (int)0x7fff7fff;      // (padding pieces: never inside the image)
+    }
+    // dY piece i = tid + 256k: slot, column and channel chunk do not depend on k, the row advances by 2 per k
+    const int rd = a.dy_ps > 1 ? a.dy_ps : 1;
+    const int d_ix = (tid >> 3) & 15, d_iy0 = tid >> 7;
+    const int d_c = cob * 8 + ((tid & 7) ^ swz(d_ix));
+    const bool d_cok = d_c < nch_d;
+    int dconst, dkstride;
+    {
+      const int Csd = a.Cout / (rd * rd);
+      const int k0 = d_c * CH;
+      const int ij = k0 / Csd, c0 = k0 - ij * Csd;
+      const int si = ij / rd, sj = ij - si * rd;
+      dconst = (((d_iy0 * rd + si) * (W * rd) + d_ix * rd + sj) * a.dy_pitch + a.dy_coff + c0) * ESZ;
+      dkstride = 2 * rd * (W * rd) * a.dy_pitch * ESZ;
+    }
+    // one tile's DMA = 6 halo pieces + 4 dY pieces per lane, in one burst behind the barrier that frees the tile's buffer
+    struct TileAddr { int y0, x0, xbase, dbase; bool colok, live; unsigned Xb; };   // Xb: LDS byte address of the buffer; live: a tile of this workgroup
+    // The workgroup's tiles are consecutive in (n, tY, tX) order, so the position of the next tile to request advances by counters: one division pair here,
+    // none per tile.  Past the end the counters run on (at most AHEAD tiles); such a tile is not `live` and every piece of it is an out-of-range offset.
+    int nx_tX = t0 % tilesX, nx_tY = (t0 / tilesX) % tilesY, nx_n = (t0 / tilesX) / tilesY;
+    auto dma_tile = [&](int it_) {              // the tiles are asked for in order: it_ = 0, 1, 2, ...
+      TileAddr t;
+      t.live = it_ < nt;
+      t.y0 = nx_tY * TH; t.x0 = nx_tX * 16;
+      const int row = nx_n * H + t.y0;
+      t.xbase = ((row * W + t.x0) * a.x_pitch) * ESZ;
+      t.dbase = ((row * rd * (W * rd) + t.x0 * rd) * a.dy_pitch) * ESZ;
+      t.colok = t.live && d_cok && (t.x0 + d_ix < W);
+      t.Xb = lds0 + (unsigned)((it_ & (NBUF - 1)) * BUF_BYTES);
+      const bool wx = nx_tX + 1 == tilesX;
+      nx_tX = wx ? 0 : nx_tX + 1;
+      nx_tY += wx ? 1 : 0;
+      const bool wy = nx_tY == tilesY;
+      nx_tY = wy ? 0 : nx_tY;
+      nx_n += wy ? 1 : 0;
 #pragma unroll
-    for (int k = 0; k < NPK; ++k) dma_x_piece(t, k);
+      for (int k = 0; k < NPK; ++k) {
+        const int gy = t.y0 + (int)(short)(pyx[k] & 0xffff), gx = t.x0 + (pyx[k] >> 16);
+        const bool ok = t.live && (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W;
+        const unsigned voff = ok ? (unsigned)(t.xbase + pconst[k]) : 0x80000000u;
+        dma16_hidden(xrs, voff, __builtin_amdgcn_readfirstlane(t.Xb + ((k * GT + hw * 64) << 4)));
+        if (SRK_WG_HELPER_SLEEP) __builtin_amdgcn_s_sleep(SRK_WG_HELPER_SLEEP);
+      }
 #pragma unroll
-    for (int k = 0; k < NDK; ++k) dma_d_piece(t, k);
-  };
+      for (int k = 0; k < NDK; ++k) {
+        const bool ok = t.colok && (t.y0 + d_iy0 + 2 * k < H);
+        const unsigned voff = ok ? (unsigned)(t.dbase + dconst + k * dkstride) : 0x80000000u;
+        dma16_hidden(drs, voff, __builtin_amdgcn_readfirstlane(t.Xb + XS_PAD + ((k * GT + hw * 64) << 4)));
+        if (SRK_WG_HELPER_SLEEP) __builtin_amdgcn_s_sleep(SRK_WG_HELPER_SLEEP);
+      }
+    };
+    float bsum8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 
+#pragma unroll
+    for (int k = 0; k < AHEAD; ++k) dma_tile(k);            // tiles 0 .. 2 (past-the-end ones as out-of-range pieces)
+    asm volatile("s_waitcnt vmcnt(%0)" :: "n"((AHEAD - 1) * PPT) : "memory");     // tile 0 landed; the two younger tiles stay in flight
+    __builtin_amdgcn_s_barrier();                           // prologue barrier: ... for every helper
+#pragma unroll 1
+    for (int it = 0; it < nt; ++it) {
+      SRK_GSTAMP(0);
+      dma_tile(it + AHEAD);                                 // into the buffer of tile it - 1, which every compute wave left before B(it - 1)
+      if (BIAS) {
+        // bias gradient: lane owns LDS slot (tid&7) of pixels (tid>>3) + 32k; the slot's channel chunk is the same
+        // for all 4 of them (the swizzle depends on the column, and 32 pixels = 2 full rows).  k = 0..3 within a tile, tiles in order.
+        const char* const Ds = smem + (it & (NBUF - 1)) * BUF_BYTES + XS_PAD;
+#pragma unroll
+        for (int k = 0; k < NDK; ++k) {
+          const i32x4 braw = lds_read16(Ds + ((tid + 256 * k) << 4));
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const uint32_t w = (uint32_t)braw[i];
+            add_f32_unpacked(bsum8[2 * i], Tr::to_f32((uint16_t)(w & 0xffff)));
+            add_f32_unpacked(bsum8[2 * i + 1], Tr::to_f32((uint16_t)(w >> 16)));
+          }
+        }
+      }
+      // exactly the two younger tiles (it + 2, it + 3) may stay in flight: this wave's pieces of tile it + 1 landed, and its reads of tile it are done
+      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_waitcnt vmcnt(%0)" :: "n"((AHEAD - 1) * PPT) : "memory");
+      SRK_GSTAMP(1);
+      __builtin_amdgcn_s_barrier();                         // B(it)
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // the past-the-end pieces (zero fill) are LDS writes too: done before the buffers are reused
+    if (BIAS) {
+      // fixed-order reduction of the per-lane chunk sums: channel c lives in chunk c>>3, held by the 32 lanes
+      // (hi, q16) with slot (c>>3) ^ swz(q16)
+      float* const bred = reinterpret_cast<float*>(smem);      // [256][8]
+      __syncthreads();                                      // every DMA landed, every compute wave past its last fragment read
+#pragma unroll
+      for (int e = 0; e < 8; ++e) bred[tid * 8 + e] = bsum8[e];
+      __syncthreads();
+      if (tid < 64) {
+        const int ch = tid >> 3, e = tid & 7;
+        float t = 0.f;
+        for (int p0 = 0; p0 < 32; ++p0) t += bred[((p0 << 3) + (ch ^ swz(p0 & 15))) * 8 + e];
+        const int c = cob * 64 + tid;
+        if (c < a.Cout) a.dbp[(size_t)slot * a.Cout + c] = t;
+      }
+    }
+    return;
+  }
+
+  // =============================== compute wave: fragment reads and MFMAs ===============================
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int rb = wave >> 1, cbk = wave & 1;
   f32x16 acc[9];
 #pragma unroll
   for (int t = 0; t < 9; ++t)
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc[t][e] = 0.f;
-  float bsum8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   int xoff[KS][2], doff[2];
 #pragma unroll
   for (int kw = 0; kw < KS; ++kw) {
@@ -570,14 +647,14 @@ SRK_DEV void wgrad_ws_body8(const srk_wgrad_args& a, const int slot, const int c
         pxf[rr][kw] = tr_read2(Xb + xoff[kw][0] + rr * (C::PITCH * 128), Xb + xoff[kw][1] + rr * (C::PITCH * 128));
   };
 
-#pragma unroll
-  for (int k = 0; k < AHEAD; ++k) dma_tile(k);            // tiles 0 .. 2 (past-the-end ones as out-of-range pieces)
-  TileAddr nxt = tile_addr(AHEAD);                        // the tile requested during tile 0
-  asm volatile("s_waitcnt vmcnt(%0)" :: "n"((AHEAD - 1) * PPT) : "memory");     // tile 0 landed; the two younger tiles stay in flight
-  __builtin_amdgcn_s_barrier();                           // ... for every wave
+  if (SRK_WG_COMPUTE_PRIO) __builtin_amdgcn_s_setprio(SRK_WG_COMPUTE_PRIO);
+  asm volatile("" ::: "memory");
+  __builtin_amdgcn_s_barrier();                           // prologue barrier: tile 0 landed for every helper
+  asm volatile("" ::: "memory");
   read_first_frags(smem);
 #pragma unroll 1
   for (int it = 0; it < nt; ++it) {
+    SRK_GSTAMP(0);
     const char* const Xs = smem + (it & (NBUF - 1)) * BUF_BYTES;
     const char* const Ds = Xs + XS_PAD;
     const char* const Xn = smem + ((it + 1) & (NBUF - 1)) * BUF_BYTES;      // tile it + 1 (past the end: a zero-filled buffer, read and never used)
@@ -590,10 +667,6 @@ SRK_DEV void wgrad_ws_body8(const srk_wgrad_args& a, const int slot, const int c
 #pragma unroll
       for (int kw = 0; kw < KS; ++kw) xf[rr][kw] = pxf[rr][kw];
     i32x4 bf = pbf;
-    // bias gradient: lane owns LDS slot (tid&7) of pixels (tid>>3) + 32k; the slot's channel chunk is the same
-    // for all 4 of them (the swizzle depends on the column, and 32 pixels = 2 full rows).  Word k is read in row k and added in row k + 1.
-    i32x4 braw = {0, 0, 0, 0};
-    TileAddr nn = nxt;
 #pragma unroll
     for (int y = 0; y < TH; ++y) {
       i32x4 bfn = bf;
@@ -604,32 +677,18 @@ SRK_DEV void wgrad_ws_body8(const srk_wgrad_args& a, const int slot, const int c
           xf[nr & 3][kw] = tr_read2(Xs + xoff[kw][0] + nr * (C::PITCH * 128), Xs + xoff[kw][1] + nr * (C::PITCH * 128));
         bfn = tr_read2(Ds + doff[0] + (y + 1) * (16 * 128), Ds + doff[1] + (y + 1) * (16 * 128));
       }
-      const i32x4 bprev = braw;
-      if (BIAS && y < NDK) braw = lds_read16(Ds + ((tid + 256 * y) << 4));
 #pragma unroll
       for (int t = 0; t < 9; ++t) {
         const int kh = t / KS, kw = t - kh * KS;
         acc[t] = Tr::mma(xf[(y + kh) & 3][kw], bf, acc[t]);
-        // the DMA of tile it + 3, front-loaded (one halo piece per row in rows 0-5, one gradient piece in rows 0-3): a piece takes 3-5k cycles
-        // to land under load
-        if (t == 1 && y < NPK) dma_x_piece(nxt, y);
-        if (t == 5 && y < NDK) dma_d_piece(nxt, y);
-        if (BIAS && y >= 1 && y <= NDK && t >= 2 && t != 5 && t <= 6) {
-          const int i = t - 2 - (t > 5 ? 1 : 0);         // t = 2, 3, 4, 6: 32-bit word i of the 16-byte word read in row y - 1
-          const uint32_t w = (uint32_t)bprev[i];
-          add_f32_unpacked(bsum8[2 * i], Tr::to_f32((uint16_t)(w & 0xffff)));
-          add_f32_unpacked(bsum8[2 * i + 1], Tr::to_f32((uint16_t)(w >> 16)));
-        }
-        if (y == TH - 2 && t == 3) nn = tile_addr(it + 1 + AHEAD);       // position of the tile the NEXT tile requests: scalar work beside MFMAs
         if (y == TH - 1 && t == 0) {
-          // ---- the seam.  This row's fragments were requested in row 6: with lgkmcnt(0) this wave has finished reading tile `it`'s buffer.
-          // Tile it + 3's ten pieces went out in rows 0-5 of this tile and nothing since, so exactly the two younger tiles (it + 2, it + 3) may
-          // stay in flight: vmcnt((AHEAD - 1) * PPT) means this wave's pieces of tile it + 1 landed.  After the barrier that holds for every
-          // wave, and every wave has all of tile `it` in registers: its buffer is free for the DMA of tile it + 4, which starts in row 0 of
-          // tile it + 1.  One MFMA is in the pipe in front of the barrier and one behind it; the other seven of the row cover the 20 reads.
+          // ---- the seam.  This row's fragments were requested in row 6: with lgkmcnt(0) this wave has finished reading tile `it`'s buffer.  Behind
+          // the barrier every helper's pieces of tile it + 1 have landed, and every compute wave has all of tile `it` in registers: its buffer is free
+          // for the DMA of tile it + 4.  One MFMA is in the pipe in front of the barrier and one behind it; the other seven of the row cover the 20 reads.
           __builtin_amdgcn_sched_barrier(0);
-          asm volatile("s_waitcnt lgkmcnt(0)\n\ts_waitcnt vmcnt(%0)" :: "n"((AHEAD - 1) * PPT) : "memory");
-          __builtin_amdgcn_s_barrier();
+          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+          SRK_GSTAMP(1);
+          __builtin_amdgcn_s_barrier();                   // B(it)
           __builtin_amdgcn_sched_barrier(0);
         }
         if (y == TH - 1 && t == 1) {                      // (one more MFMA goes into the pipe before the reads: none of them stands between the barrier and an MFMA)
@@ -640,10 +699,8 @@ SRK_DEV void wgrad_ws_body8(const srk_wgrad_args& a, const int slot, const int c
       bf = bfn;
       __builtin_amdgcn_sched_barrier(0);
     }
-    nxt = nn;
   }
 
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // the past-the-end pieces (zero fill) are LDS writes too: done before the buffers are reused
   // ---- store the workgroup's slab (row-contiguous 128-byte segments per half wave) ------------------------
   // buffer stores: one 32-bit offset per lane, the (tap, row) part is uniform; rows / columns beyond the real
   // channel counts get an out-of-range offset (dropped by the hardware) instead of a branch
@@ -664,39 +721,34 @@ SRK_DEV void wgrad_ws_body8(const srk_wgrad_args& a, const int slot, const int c
       }
     }
   }
-  if (BIAS) {
-    // fixed-order reduction of the per-lane chunk sums: channel c lives in chunk c>>3, held by the 32 lanes
-    // (hi, q16) with slot (c>>3) ^ swz(q16)
-    float* const bred = reinterpret_cast<float*>(smem);      // [256][8]
+  if (BIAS) {             // the two barriers of the helpers' bias reduction (the first one: this wave's last fragment reads are done)
     __syncthreads();
-#pragma unroll
-    for (int e = 0; e < 8; ++e) bred[tid * 8 + e] = bsum8[e];
     __syncthreads();
-    if (tid < 64) {
-      const int ch = tid >> 3, e = tid & 7;
-      float t = 0.f;
-      for (int p0 = 0; p0 < 32; ++p0) t += bred[((p0 << 3) + (ch ^ swz(p0 & 15))) * 8 + e];
-      const int c = cob * 64 + tid;
-      if (c < a.Cout) a.dbp[(size_t)slot * a.Cout + c] = t;
-    }
   }
+#undef SRK_GSTAMP
 }
 
 // the 8-row body with or without the bias sum: one uniform branch per workgroup instead of one per tile
 template <int DT>
 SRK_DEV void wgrad_ws_run8(const srk_wgrad_args& a, const int slot, const int cib, const int cob, const int tilesX, const int tilesY,
-                          const unsigned x_bytes, const unsigned dy_bytes, const int tq, const int trem, char* const smem) {
-  if (a.dbp != nullptr && cib == 0) wgrad_ws_body8<DT, true>(a, slot, cib, cob, tilesX, tilesY, x_bytes, dy_bytes, tq, trem, smem);
-  else wgrad_ws_body8<DT, false>(a, slot, cib, cob, tilesX, tilesY, x_bytes, dy_bytes, tq, trem, smem);
+                          const unsigned x_bytes, const unsigned dy_bytes, const int tq, const int trem, char* const smem, const bool single) {
+  if (a.dbp != nullptr && cib == 0) wgrad_ws_body8<DT, true>(a, slot, cib, cob, tilesX, tilesY, x_bytes, dy_bytes, tq, trem, smem, single);
+  else wgrad_ws_body8<DT, false>(a, slot, cib, cob, tilesX, tilesY, x_bytes, dy_bytes, tq, trem, smem, single);
 }
 
+// One entry point per tile height (th is uniform over a launch: ws_tile_height, srk_wgrad_group_plan; the host picks the kernel): the 16-row form keeps
+// 256 threads and the whole register file, the 8-row form is 512 threads at two waves per SIMD.
 template <int DT>
-__global__ __launch_bounds__(256, 1) void conv_wgrad_ws_kernel(const srk_wgrad_args a, int tilesX, int tilesY, int th,
+__global__ __launch_bounds__(256, 1) void conv_wgrad_ws_kernel(const srk_wgrad_args a, int tilesX, int tilesY,
                                                                 unsigned x_bytes, unsigned dy_bytes, int tq, int trem) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  // th: tile height the host cut the images with (ws_tile_height: 8 = the four-buffer ring, 16 = two buffers); uniform over the launch
-  if (th == WS_TH) wgrad_ws_run8<DT>(a, blockIdx.x, blockIdx.y, blockIdx.z, tilesX, tilesY, x_bytes, dy_bytes, tq, trem, smem);
-  else wgrad_ws_body16<DT>(a, blockIdx.x, blockIdx.y, blockIdx.z, tilesX, tilesY, x_bytes, dy_bytes, tq, trem, smem);
+  wgrad_ws_body16<DT>(a, blockIdx.x, blockIdx.y, blockIdx.z, tilesX, tilesY, x_bytes, dy_bytes, tq, trem, smem);
+}
+template <int DT>
+__global__ __launch_bounds__(WS8_THREADS, 2) void conv_wgrad_ws8_kernel(const srk_wgrad_args a, int tilesX, int tilesY,
+                                                                         unsigned x_bytes, unsigned dy_bytes, int tq, int trem) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  wgrad_ws_run8<DT>(a, blockIdx.x, blockIdx.y, blockIdx.z, tilesX, tilesY, x_bytes, dy_bytes, tq, trem, smem, true);
 }
 
 // ---- grouped launch: the weight gradients of MANY convolutions in one dispatch ---------------------------------------------
@@ -715,9 +767,9 @@ struct WgJob {
   int block0, th;           // th: tile height of this launch (all jobs of a launch: ws_tile_height of the largest one)
 };
 
-template <int DT>
-__global__ __launch_bounds__(256, 1) void conv_wgrad_ws_group_kernel(const WgJob* __restrict__ jobs, const int* __restrict__ block_job) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
+// block id -> (job, slot, ci block, co block)
+struct WgBlock { int slot, cib, cob; };
+SRK_DEV WgBlock wgrad_group_block(const WgJob* __restrict__ jobs, const int* __restrict__ block_job, WgJob& j) {
   // The (ci block, co block) workgroups of one tile range read the SAME X and dY tiles.  The hardware deals consecutive block ids to the eight XCDs in turn
   // (each with its own L2), so the logical index is (XCD, slot in the XCD): the ncib x ncob blocks of a range share one L2 (cf. conv_ks.hip).  Any grid size:
   // XCD x holds ceil((G - x) / 8) blocks.  (SRK_WGRAD_XCD_REMAP=0: A/B builds.)
@@ -730,13 +782,34 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_ws_group_kernel(const WgJob
     lb = x * q + (x < r ? x : r) + (blockIdx.x >> 3);
   }
   const int jid = block_job[lb];
-  const WgJob j = jobs[jid];
+  j = jobs[jid];
   const int local = (int)lb - j.block0;
   const int per = j.ncib * j.ncob;
-  const int slot = local / per, rem = local - slot * per;
-  const int cib = rem / j.ncob, cob = rem - cib * j.ncob;
-  if (j.th == WS_TH) wgrad_ws_run8<DT>(j.a, slot, cib, cob, j.tilesX, j.tilesY, j.x_bytes, j.dy_bytes, j.tq, j.trem, smem);
-  else wgrad_ws_body16<DT>(j.a, slot, cib, cob, j.tilesX, j.tilesY, j.x_bytes, j.dy_bytes, j.tq, j.trem, smem);
+  WgBlock b;
+  b.slot = local / per;
+  const int rem = local - b.slot * per;
+  b.cib = rem / j.ncob;
+  b.cob = rem - b.cib * j.ncob;
+  return b;
+}
+
+// One entry point per tile height, as for the single launch; srk_conv2d_wgrad_group picks by the height its plan recorded.  (A table of the other height
+// never reaches a kernel -- the launcher refuses a launch without its plan; the test on j.th only keeps a kernel from walking tiles cut for the other one.)
+template <int DT>
+__global__ __launch_bounds__(256, 1) void conv_wgrad_ws_group_kernel(const WgJob* __restrict__ jobs, const int* __restrict__ block_job) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  WgJob j;
+  const WgBlock b = wgrad_group_block(jobs, block_job, j);
+  if (j.th == WS_TH) return;
+  wgrad_ws_body16<DT>(j.a, b.slot, b.cib, b.cob, j.tilesX, j.tilesY, j.x_bytes, j.dy_bytes, j.tq, j.trem, smem);
+}
+template <int DT>
+__global__ __launch_bounds__(WS8_THREADS, 2) void conv_wgrad_ws8_group_kernel(const WgJob* __restrict__ jobs, const int* __restrict__ block_job) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  WgJob j;
+  const WgBlock b = wgrad_group_block(jobs, block_job, j);
+  if (j.th != WS_TH) return;
+  wgrad_ws_run8<DT>(j.a, b.slot, b.cib, b.cob, j.tilesX, j.tilesY, j.x_bytes, j.dy_bytes, j.tq, j.trem, smem, false);
 }
 
 // =================================================================================================
@@ -1050,9 +1123,11 @@ template <int DT> int launch_ws(const srk_wgrad_args& a, hipStream_t st, int sla
   constexpr int LDS = WS_LDS_BYTES;
   static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_ws_kernel<DT>),
                                                      hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-  if (attr != hipSuccess) {
-    srk_set_error("srk_conv2d_wgrad(ws): cannot reserve %d bytes of LDS: %s", LDS, hipGetErrorString(attr));
-    return (int)attr;
+  static const hipError_t attr8 = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_ws8_kernel<DT>),
+                                                      hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+  if (attr != hipSuccess || attr8 != hipSuccess) {
+    srk_set_error("srk_conv2d_wgrad(ws): cannot reserve %d bytes of LDS: %s", LDS, hipGetErrorString(attr != hipSuccess ? attr : attr8));
+    return (int)(attr != hipSuccess ? attr : attr8);
   }
   const int th = ws_tile_height(a.N, a.H, a.W);
   const int tilesX = (a.W + 15) / 16, tilesY = (a.H + th - 1) / th;
@@ -1062,8 +1137,12 @@ template <int DT> int launch_ws(const srk_wgrad_args& a, hipStream_t st, int sla
   const unsigned xb = (unsigned)((long long)a.N * a.H * a.W * a.x_pitch * 2);
   const unsigned db = (unsigned)((long long)a.N * a.H * a.W * rd * rd * a.dy_pitch * 2);
   srk_kernel_name = "wgrad_ws";
-  hipLaunchKernelGGL((conv_wgrad_ws_kernel<DT>), dim3(slabs, cib, cob), dim3(256), LDS, st, a, tilesX, tilesY, th, xb, db,
-                     (int)(ntiles / slabs), (int)(ntiles % slabs));
+  if (th == WS_TH)
+    hipLaunchKernelGGL((conv_wgrad_ws8_kernel<DT>), dim3(slabs, cib, cob), dim3(WS8_THREADS), LDS, st, a, tilesX, tilesY, xb, db,
+                       (int)(ntiles / slabs), (int)(ntiles % slabs));
+  else
+    hipLaunchKernelGGL((conv_wgrad_ws_kernel<DT>), dim3(slabs, cib, cob), dim3(256), LDS, st, a, tilesX, tilesY, xb, db,
+                       (int)(ntiles / slabs), (int)(ntiles % slabs));
   SRK_LAUNCH_CHECK();
   return 0;
 }
@@ -1179,6 +1258,29 @@ extern "C" int srk_wgrad_group_ok(const srk_wgrad_args* a) {
   return (a && a->KH == 3 && a->KW == 3 && a->N > 0 && wgrad_ws_slabs(*a) > 0) ? 1 : 0;
 }
 
+// The tile height of a grouped launch is decided by its plan, and the launch receives the plan only as device tables: the table pass of
+// srk_wgrad_group_plan leaves (blocks, tile height) here and srk_conv2d_wgrad_group picks its kernel by the newest entry with its block count.
+// A launch without a plan in this process is refused.
+namespace {
+struct WgPlanNote { int nblocks, th; };
+constexpr int WG_PLAN_NOTES = 16;
+std::mutex wg_plan_mutex;
+WgPlanNote wg_plan_notes[WG_PLAN_NOTES];
+unsigned wg_plan_count = 0;
+void wg_plan_record(int nblocks, int th) {
+  std::lock_guard<std::mutex> g(wg_plan_mutex);
+  wg_plan_notes[wg_plan_count++ % WG_PLAN_NOTES] = WgPlanNote{nblocks, th};
+}
+int wg_plan_lookup(int nblocks) {              // 0: no such plan
+  std::lock_guard<std::mutex> g(wg_plan_mutex);
+  for (unsigned k = 0; k < WG_PLAN_NOTES && k < wg_plan_count; ++k) {
+    const WgPlanNote& n = wg_plan_notes[(wg_plan_count - 1 - k) % WG_PLAN_NOTES];
+    if (n.nblocks == nblocks) return n.th;
+  }
+  return 0;
+}
+}  // namespace
+
 extern "C" int srk_wgrad_group_plan(srk_wgrad_args* jobs, int n, float* scratch, void* table_host, int* block_job_host,
                                     int* nblocks_out, long long* scratch_floats_out) {
   SRK_CHECK_ARG(jobs && n > 0 && nblocks_out && scratch_floats_out, "srk_wgrad_group_plan: null pointer / no jobs");
@@ -1257,26 +1359,35 @@ extern "C" int srk_wgrad_group_plan(srk_wgrad_args* jobs, int n, float* scratch,
   SRK_CHECK_ARG(nb < 0x7fffffffLL, "srk_wgrad_group_plan: %lld blocks", nb);
   *nblocks_out = (int)nb;
   *scratch_floats_out = off;
+  if (tab) wg_plan_record((int)nb, th);
   return 0;
 }
 
 extern "C" int srk_conv2d_wgrad_group(const void* table_dev, const int* block_job_dev, int nblocks, int dtype, srk_stream_t stream) {
   SRK_CHECK_ARG(table_dev && block_job_dev && nblocks > 0, "srk_conv2d_wgrad_group: null pointer / no blocks");
   SRK_CHECK_ARG(dtype == SRK_BF16 || dtype == SRK_F16, "srk_conv2d_wgrad_group: 16-bit dtypes only");
-  typedef WgCfg<SRK_BF16, 3> C;
   constexpr int LDS = WS_LDS_BYTES;
-  static const hipError_t attr0 = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_ws_group_kernel<SRK_BF16>),
-                                                      hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-  static const hipError_t attr1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_ws_group_kernel<SRK_F16>),
-                                                      hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-  if (attr0 != hipSuccess || attr1 != hipSuccess) {
-    srk_set_error("srk_conv2d_wgrad_group: cannot reserve %d bytes of LDS", LDS);
-    return (int)(attr0 != hipSuccess ? attr0 : attr1);
-  }
+  static const hipError_t attrs[4] = {
+      hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_ws_group_kernel<SRK_BF16>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS),
+      hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_ws_group_kernel<SRK_F16>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS),
+      hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_ws8_group_kernel<SRK_BF16>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS),
+      hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_ws8_group_kernel<SRK_F16>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS)};
+  for (int k = 0; k < 4; ++k)
+    if (attrs[k] != hipSuccess) {
+      srk_set_error("srk_conv2d_wgrad_group: cannot reserve %d bytes of LDS", LDS);
+      return (int)attrs[k];
+    }
+  const int th = wg_plan_lookup(nblocks);
+  SRK_CHECK_ARG(th != 0, "srk_conv2d_wgrad_group: no srk_wgrad_group_plan of %d blocks precedes this launch", nblocks);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const WgJob* tab = reinterpret_cast<const WgJob*>(table_dev);
-  if (dtype == SRK_BF16) hipLaunchKernelGGL((conv_wgrad_ws_group_kernel<SRK_BF16>), dim3(nblocks), dim3(256), LDS, st, tab, block_job_dev);
-  else hipLaunchKernelGGL((conv_wgrad_ws_group_kernel<SRK_F16>), dim3(nblocks), dim3(256), LDS, st, tab, block_job_dev);
+  if (th == WS_TH) {
+    if (dtype == SRK_BF16) hipLaunchKernelGGL((conv_wgrad_ws8_group_kernel<SRK_BF16>), dim3(nblocks), dim3(WS8_THREADS), LDS, st, tab, block_job_dev);
+    else hipLaunchKernelGGL((conv_wgrad_ws8_group_kernel<SRK_F16>), dim3(nblocks), dim3(WS8_THREADS), LDS, st, tab, block_job_dev);
+  } else {
+    if (dtype == SRK_BF16) hipLaunchKernelGGL((conv_wgrad_ws_group_kernel<SRK_BF16>), dim3(nblocks), dim3(256), LDS, st, tab, block_job_dev);
+    else hipLaunchKernelGGL((conv_wgrad_ws_group_kernel<SRK_F16>), dim3(nblocks), dim3(256), LDS, st, tab, block_job_dev);
+  }
   SRK_LAUNCH_CHECK();
   return 0;
 }
