@@ -3,13 +3,21 @@
 // gradient.  The generic path (generic.hip) materialises the K*K-times larger column tensor in HBM (6.1 GB per batch of 16 for
 // this layer: 8 of SRResNet's 11.9 ms per step); here the (16 + K - 1)^2 halo tile sits in LDS once and all K*K taps read it at
 // shifted addresses, exactly as the 3x3 kernels do, with the weights of one KERNEL ROW (K taps) at a time streaming through a
-// two-slot LDS ring by hidden LDS-DMA.
-//   lk_conv_kernel<DT, CPP, NRB>  forward (CPP = 8: 64 input channels, NRB = 1: <= 32 output rows) and, with data-gradient packs,
-//                                 dgrad (CPP = 2: 16 stored gradient channels, NRB = 2: 64 rows).  4 waves x 64 pixels of a 16x16 tile.
-//   lk_wgrad_kernel<DT>           dW[tap][ci][co]: a workgroup owns ONE kernel row (K taps x 64 input channels x 16 gradient
-//                                 channels = 18 accumulator tiles over its 4 waves) and a range of tiles; K = the 16 pixels of a tile
-//                                 row, both operands by the transposing LDS read; partial sums to per-workgroup slabs
-//                                 (srk_wgrad_finalize's layout).
+// two-slot LDS ring by hidden LDS-DMA.  Each kernel's struct states its geometry (tile, halo pitch, every LDS buffer's offset and size,
+// ring depth, LDS_BYTES, the host's tile count) ONCE, for the kernel and for its launcher:
+//   lk_conv_kernel<DT, CPP, NRB, K>   LkConvCfg     forward (CPP = 8: 64 input channels, NRB = 1: <= 32 output rows) and, with data-gradient packs,
+//                                                   dgrad (CPP = 2: 16 stored gradient channels, NRB = 2: 64 rows).  4 waves x 64 pixels of a 16x16 tile.
+//   lk_conv_rows_kernel<DT, K>        LkRowsCfg     forward with <= 4 real output channels: (kw, co) pairs on the MFMA rows
+//   lk_wgrad_kernel<DT, K>            LkWgradCfg    dW[tap][ci][co]: a workgroup owns ONE kernel row (K taps x 64 input channels x 16 gradient channels
+//                                                   = 18 accumulator tiles over its 4 waves) and a range of tiles; K = the 16 pixels of a tile row, both
+//                                                   operands by the transposing LDS read; partial sums to per-workgroup slabs (srk_wgrad_finalize's layout).
+//   lk_wgrad_packed_kernel<DT, K>     LkPackedCfg   the same for <= 6 real output channels: (kw, co) pairs on the MFMA columns
+//   lk_wgrad_allrows_kernel<DT, K>    LkAllRowsCfg  ... <= 4 real output channels, all K kernel rows in one workgroup, compact slabs
+//   lk5_fwd_kernel<DT>                Lk5FwdCfg     the collapsed HR stage's 5x5 image conv (hr_tail.hip), a tap per MFMA (4 colours)
+//   lk5_rows_fwd_kernel<DT, NW>       Lk5RowsCfg    ... (kernel column, channel) pairs on the MFMA rows (1-3 colours)
+//   lk5_dgrad_kernel<DT>, lk5_wgrad_kernel<DT>      Lk5DgradCfg, Lk5WgradCfg: its data and weight gradients
+// The kernels keep their own copies of the halo-DMA descriptor loops and of the few-channel transposition: moved into shared device functions,
+// however they were passed their arguments, hipcc generated other code for every kernel that called them (tools/isa_compare.py).
 // Packed weights, epilogue order and slab format are srk_conv2d's / srk_conv2d_wgrad's: those entry points dispatch here.
 #include <stdlib.h>
 #include <type_traits>
@@ -22,28 +30,118 @@
 
 namespace {
 
+// ---- geometry ------------------------------------------------------------------------------------------------------------------
+constexpr int LK_LDS_MAX = 160 * 1024;
+constexpr int lk_kb(int bytes) { return (bytes + 1023) & ~1023; }      // whole 1 KB DMA pieces
+// an image in tiles of TH x 16 output pixels
+template <int TH_> struct LkGrid {
+  static constexpr int TH = TH_;
+  static int tiles_x(int W) { return (W + 15) / 16; }
+  static int tiles_y(int H) { return (H + TH - 1) / TH; }
+  static long long tiles(int N, int H, int W) { return (long long)N * tiles_y(H) * tiles_x(W); }
+};
+// the swizzled 128-byte-per-pixel LDS image (srk_common.h) of the ROWS x (16 + K - 1) input pixels under a tile, in 1 KB DMA pieces
+template <int K, int ROWS_> struct LkHalo {
+  static constexpr int ROWS = ROWS_, XW = 16 + K - 1, XWP = (XW + 1) & ~1;      // even row pitch
+  static constexpr int ROWB = XWP * 128, BYTES = lk_kb(ROWS * ROWB);
+  static constexpr int NPX = BYTES / 1024, XPW = (NPX + 3) / 4;                 // pieces; pieces per wave
+};
+// the gradient tile's channel planes of the few-real-output-channels weight gradients: DT[co][y][col + K - 1], two bytes a value, K - 1
+// zero columns on both sides (+ 16 for the second column block's reads), planes 0 .. cr - 1 real and plane cr all zero
+template <int K, int TH_> struct LkPlanes {
+  static constexpr int TH = TH_, DTW = 16 + 2 * (K - 1) + 16, DTP = DTW * 2;      // plane row: columns -(K-1) .. 16 + (K-1) + 15
+  static constexpr int NPL = 8, PLANE = TH * DTP, BYTES = NPL * PLANE;          // <= 6 real planes + the zero plane
+};
+template <int CPP_, int NRB, int K> struct LkConvCfg : LkGrid<16> {
+  static constexpr int CPP = CPP_, PXB = CPP * 16, ROWS = 32 * NRB;             // bytes per pixel in the LDS tile; MFMA rows
+  static constexpr int XT = 16 + K - 1, XTP = (XT + 1) & ~1;                    // halo tile edge, even row pitch
+  static constexpr int X_PIECES = (XT * XTP * CPP + 63) / 64;
+  static constexpr int SLAB = K * CPP * ROWS * 16, RING = 2;                    // one kernel row of packed weights; slots of them
+  static constexpr int W_OFF = lk_kb(XT * XTP * PXB), W_BYTES = K * SLAB;       // the ring behind the tile; the packed weights in HBM
+  static constexpr int LDS_BYTES = W_OFF + RING * SLAB;
+  static_assert(SLAB % 1024 == 0, "a slab is whole 1 KB pieces (ROWS >= 32, CPP >= 2)");
+};
+template <int K> struct LkRowsCfg : LkGrid<8> {
+  typedef LkHalo<K, TH + K - 1> Halo;
+  static constexpr int PW_OFF = Halo::BYTES, PW_BYTES = 32 * 32 * 4;            // per wave: [32 rows][32 columns] fp32
+  static constexpr int OW_OFF = PW_OFF + 4 * PW_BYTES, OW_BYTES = 16 * 16 * 2;  // per wave: [16 pixels][16 stored channels] of one output row
+  static constexpr int LDS_BYTES = OW_OFF + 4 * OW_BYTES;
+};
+template <int K> struct LkWgradCfg : LkGrid<16> {
+  typedef LkHalo<K, 16> Halo;                                                   // the 16 rows one kernel row touches
+  static constexpr int D_BYTES = 16 * 16 * 32, ND = D_BYTES / 1024 + 1;         // gradient tile, 32 bytes per pixel (16 channels), + 1 KB of zeros
+  static constexpr int D_OFF = Halo::BYTES, BUF = D_OFF + ND * 1024, RING = 2;
+  static constexpr int LDS_BYTES = RING * BUF;
+};
+template <int K> struct LkPackedCfg : LkGrid<16> {
+  typedef LkHalo<K, 16> Halo;
+  typedef LkPlanes<K, 16> Planes;
+  static constexpr int D_BYTES = 16 * 16 * 32, ND = D_BYTES / 1024, MAXC = 6;   // gradient tile; the most real output channels
+  static constexpr int D_OFF = Halo::BYTES, BUF = D_OFF + D_BYTES, RING = 2;
+  static constexpr int DT_OFF = RING * BUF, RED_OFF = DT_OFF + Planes::BYTES, RED_BYTES = 2 * 16 * 64 * 4;      // the s = 1 waves' sums
+  static constexpr int LDS_BYTES = RED_OFF + RED_BYTES;
+  static_assert(MAXC * 256 * 4 <= RING * BUF, "the bias block sum reuses the tile buffers");
+};
+template <int K> struct LkAllRowsCfg : LkGrid<8> {
+  typedef LkHalo<K, TH + K - 1> Halo;
+  typedef LkPlanes<K, TH> Planes;
+  static constexpr int CS = 4;                                                  // channels of a compact slab [tap][ci][CS] = the most real ones
+  static constexpr int D_BYTES = TH * 16 * 32, ND = D_BYTES / 1024;
+  static constexpr int D_OFF = Halo::BYTES, BUF = D_OFF + D_BYTES, RING = 2;
+  static constexpr int DT_OFF = RING * BUF, LDS_BYTES = DT_OFF + Planes::BYTES;
+  static_assert(K * 2 * 16 * 64 * 4 <= RING * BUF, "the final reduction reuses the tile buffers");
+};
+struct Lk5FwdCfg : LkGrid<16> {
+  static constexpr int XT = 20, XB = XT * XT * 128, NPC = XB / 1024, RING = 2;  // halo tile 51,200 B = 50 pieces of 1 KB
+  static constexpr int WB = 25 * 8 * 16 * 16, W_SRC_BYTES = 25 * 8 * 32 * 16;   // compact weights 51,200 B, in front of the tiles; the packed ones
+  static constexpr int LDS_BYTES = WB + RING * XB;
+};
+template <int NW_> struct Lk5RowsCfg {
+  static constexpr int NW = NW_, BAND = 28, AHEAD = NW == 4 ? 2 : 1, PRO = NW + 4 + (AHEAD - 1) * NW, RING = PRO + NW;
+  static constexpr int ROWB = 32 * 128, SP = 68, SCR = 32 * SP * 4;             // ring row 4,096 B; scratch [column][row], pitch 68 floats: 8,704 B per wave
+  static constexpr int SCR_OFF = RING * ROWB, LDS_BYTES = SCR_OFF + NW * SCR;
+};
+struct Lk5DgradCfg {
+  static constexpr int BAND = 32, NW = 4, RING = 16, ROWB = 36 * 32;            // ring row: 36 pixels x 32 bytes = 72 chunks
+  static constexpr int LDS_BYTES = RING * ROWB;
+};
+struct Lk5WgradCfg : LkGrid<16> {
+  static constexpr int XB = 16 * 16 * 128, DP = 20, DB = 13 * 1024, BUF = XB + DB, RING = 3;      // gradient halo: 20 x 20 x 32 B = 12,800 (+ DMA slack)
+  static constexpr int LDS_BYTES = RING * BUF;
+};
+
+// ---- shared device pieces ------------------------------------------------------------------------------------------------------
+struct LkTile { int n, y0, x0; };
+SRK_DEV LkTile lk_tile_of(int tile, int tilesX, int tilesY, int TH) {
+  const int tX = tile % tilesX;
+  tile /= tilesX;
+  const int tY = tile % tilesY;
+  return LkTile{tile / tilesY, tY * TH, tX * 16};
+}
+// a persistent workgroup's contiguous tiles: tq each, the first trem slots one more
+struct LkRange { int t0, nt; };
+SRK_DEV LkRange lk_slot_range(int slot, int tq, int trem) { return LkRange{slot * tq + min(slot, trem), tq + (slot < trem ? 1 : 0)}; }
+// the stored channels of a slab that are padding: zeros (the finalize step adds whole slabs)
+SRK_DEV void lk_few_zero_pad(float* sl, int count, int cout, int cr, int tid) {
+  for (int i = tid; i < count; i += 256)
+    if (i % cout >= cr) sl[i] = 0.f;
+}
+
 template <int DT, int CPP, int NRB, int K>
 __global__ __launch_bounds__(256) void lk_conv_kernel(const srk_conv_args a, int tilesX, int tilesY, unsigned x_bytes, unsigned w_bytes) {
   typedef DTraits<DT> Tr;
-  constexpr int PXB = CPP * 16;                                  // bytes per pixel in the LDS tile
-  constexpr int ROWS = 32 * NRB;
+  typedef LkConvCfg<CPP, NRB, K> C;
+  constexpr int PXB = C::PXB, ROWS = C::ROWS, XT = C::XT, XTP = C::XTP, slab = C::SLAB;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int XT = 16 + K - 1, XTP = (XT + 1) & ~1;           // halo tile edge, even row pitch
-  constexpr int xs_bytes = XT * XTP * PXB;
-  constexpr int slab = K * CPP * ROWS * 16;                      // one kernel row of packed weights
   char* const Xs = smem;
-  char* const Wr = smem + ((xs_bytes + 1023) & ~1023);
+  char* const Wr = smem + C::W_OFF;
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = lane & 31, h = lane >> 5;
   const int H = a.H, W = a.W, P = K / 2;
-  int pt = blockIdx.x;
-  const int tX = pt % tilesX;
-  pt /= tilesX;
-  const int tY = pt % tilesY;
-  const int n = pt / tilesY;
-  const int y0 = tY * 16, x0 = tX * 16;
+  const LkTile tl = lk_tile_of(blockIdx.x, tilesX, tilesY, C::TH);
+  const int n = tl.n, y0 = tl.y0, x0 = tl.x0;
 
   const i32x4 xrsrc = make_rsrc4(a.x, x_bytes), wrsrc = make_rsrc4(a.wpk, w_bytes);
   const unsigned xs_lds = lds_addr_of(Xs), wr_lds = lds_addr_of(Wr);
@@ -65,9 +163,8 @@ __global__ __launch_bounds__(256) void lk_conv_kernel(const srk_conv_args a, int
 
   // halo tile: 1 KB pieces of 64 / CPP pixels; chunk slot XOR-swizzled by the tile column when a pixel is a whole 128-byte row
   {
-    constexpr int npieces = (XT * XTP * CPP + 63) / 64;
 #pragma unroll 4
-    for (int k = wave; k < npieces; k += 4) {
+    for (int k = wave; k < C::X_PIECES; k += 4) {
       const int i = k * 64 + lane;
       const int sl = i % CPP, p = i / CPP;
       const int iy = p / XTP, ix = p - iy * XTP;
@@ -78,7 +175,7 @@ __global__ __launch_bounds__(256) void lk_conv_kernel(const srk_conv_args a, int
       dma16_hidden(xrsrc, voff, (unsigned)__builtin_amdgcn_readfirstlane((int)(xs_lds + (k << 10))));
     }
   }
-  constexpr int spieces = slab >> 10;                            // whole KB: K * CPP * ROWS * 16 is a multiple of 1024 for ROWS >= 32, CPP >= 2
+  constexpr int spieces = slab >> 10;
   auto dma_slab = [&](int kh) {
     const unsigned dst = wr_lds + (unsigned)((kh & 1) * slab);
     for (int k = wave; k < spieces; k += 4)
@@ -191,21 +288,22 @@ template <int DT, int K>
 __global__ __launch_bounds__(256) void lk_wgrad_kernel(const srk_wgrad_args a, int tilesX, int tilesY, int ntiles, int tq, int trem,
                                                        unsigned x_bytes, unsigned dy_bytes) {
   typedef DTraits<DT> Tr;
+  typedef LkWgradCfg<K> C;
   constexpr int MAXP = (2 * K + 3) / 4;                          // pairs per wave
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int XW = 16 + K - 1, XWP = (XW + 1) & ~1;
-  constexpr int xbuf = 16 * XWP * 128, dbuf = 16 * 16 * 32 + 1024, buf = xbuf + dbuf;   // gradient tile: 32 bytes per pixel (16 channels) + 1 KB of zeros
+  constexpr int XW = C::Halo::XW, XWP = C::Halo::XWP, xbuf = C::D_OFF, buf = C::BUF;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int slot = blockIdx.x, kh = blockIdx.y;
   const int H = a.H, W = a.W, P = K / 2;
-  const int t0 = slot * tq + min(slot, trem), nt = tq + (slot < trem ? 1 : 0);
+  const LkRange rg = lk_slot_range(slot, tq, trem);
+  const int t0 = rg.t0, nt = rg.nt;
   const i32x4 xrs = make_rsrc4(a.x, x_bytes), drs = make_rsrc4(a.dy, dy_bytes);
   const unsigned lds0 = lds_addr_of(smem);
 
   // per-lane piece constants (tile-independent): x piece k = wave + 4 j covers pixels (iy, ix) of the 16 x XWP rows, chunk c;
   // packed iy | ix << 8 | c << 16 | valid << 24
-  constexpr int NPX = 16 * XWP * 8 / 64, XPW = (NPX + 3) / 4, NPD = 9, DPW = (NPD + 3) / 4;   // + 8 gradient pieces + 1 of zeros
+  constexpr int NPX = C::Halo::NPX, XPW = C::Halo::XPW, NPD = C::ND, DPW = (NPD + 3) / 4;   // + 8 gradient pieces + 1 of zeros
   int xdesc[XPW], ddesc[DPW];
 #pragma unroll
   for (int j = 0; j < XPW; ++j) {
@@ -216,15 +314,11 @@ __global__ __launch_bounds__(256) void lk_wgrad_kernel(const srk_wgrad_args a, i
 #pragma unroll
   for (int j = 0; j < DPW; ++j) {
     const int k = wave + 4 * j, i = k * 64 + lane, c = i & 1, pp = i >> 1;          // 2 chunks per pixel, pixels row-major 16 x 16
-    ddesc[j] = (pp >> 4) | ((pp & 15) << 8) | (c << 16) | ((k < 8 && c * 8 < a.Cout) ? 1 << 24 : 0);
+    ddesc[j] = (pp >> 4) | ((pp & 15) << 8) | (c << 16) | ((k < NPD - 1 && c * 8 < a.Cout) ? 1 << 24 : 0);
   }
   auto dma_tile = [&](int tile, int b) {
-    int pt = tile;
-    const int tX = pt % tilesX;
-    pt /= tilesX;
-    const int tY = pt % tilesY;
-    const int n = pt / tilesY;
-    const int y0 = tY * 16, x0 = tX * 16;
+    const LkTile t = lk_tile_of(tile, tilesX, tilesY, C::TH);
+    const int n = t.n, y0 = t.y0, x0 = t.x0;
 #pragma unroll
     for (int j = 0; j < XPW; ++j) {
       const int k = wave + 4 * j;
@@ -266,7 +360,7 @@ __global__ __launch_bounds__(256) void lk_wgrad_kernel(const srk_wgrad_args a, i
   for (int rd = 0; rd < 2; ++rd) {
     const int G = lane >> 4, q = (lane & 15) >> 2, pq = lane & 3;
     const int col = 8 * (G >> 1) + 4 * rd + q;
-    boff[rd] = (G & 1) ? (16 * 16 * 32 + pq * 8) : (col * 32 + pq * 8);
+    boff[rd] = (G & 1) ? (C::D_BYTES + pq * 8) : (col * 32 + pq * 8);
   }
 
   const bool do_bias = a.dbp != nullptr && kh == 0 && wave == 0;     // db = sum of the gradient: from the fragments wave 0 fetches anyway
@@ -284,7 +378,7 @@ __global__ __launch_bounds__(256) void lk_wgrad_kernel(const srk_wgrad_args a, i
       bfn = tr_read2(D + yd + boff[0], D + yd + boff[1]);
 #pragma unroll
       for (int j = 0; j < MAXP; ++j)
-        if (wave + 4 * j < npairs) afn[j] = tr_read2(X + y * (XWP * 128) + aoff[j][0], X + y * (XWP * 128) + aoff[j][1]);
+        if (wave + 4 * j < npairs) afn[j] = tr_read2(X + y * C::Halo::ROWB + aoff[j][0], X + y * C::Halo::ROWB + aoff[j][1]);
     };
     fetch(0);
 #pragma unroll 2
@@ -345,27 +439,22 @@ template <int DT, int K>
 __global__ __launch_bounds__(256, 2) void lk_conv_rows_kernel(const srk_conv_args a, int tilesX, int tilesY, unsigned x_bytes, unsigned rows_off) {
   typedef DTraits<DT> Tr;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int TR = 8, XW = 16 + K - 1, XWP = (XW + 1) & ~1, XR = TR + K - 1;
-  constexpr int xbuf = (XR * XWP * 128 + 1023) & ~1023;
+  typedef LkRowsCfg<K> C;
+  constexpr int TR = C::TH, XR = C::Halo::ROWS, XW = C::Halo::XW, XWP = C::Halo::XWP, NPX = C::Halo::NPX, XPW = C::Halo::XPW;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  float* const Pw = reinterpret_cast<float*>(smem + xbuf) + wave * 1024;          // [32 rows][32 columns] fp32
-  char* const Ow = smem + xbuf + 4 * 4096 + wave * 512;                            // [16 pixels][16 stored channels] of one output row
+  float* const Pw = reinterpret_cast<float*>(smem + C::PW_OFF + wave * C::PW_BYTES);
+  char* const Ow = smem + C::OW_OFF + wave * C::OW_BYTES;
   const int H = a.H, W = a.W, P = K / 2, cr = a.cout_real;
-  int pt = blockIdx.x;
-  const int tX = pt % tilesX;
-  pt /= tilesX;
-  const int tY = pt % tilesY;
-  const int n = pt / tilesY;
-  const int y0 = tY * TR, x0 = tX * 16;
+  const LkTile tl = lk_tile_of(blockIdx.x, tilesX, tilesY, TR);
+  const int n = tl.n, y0 = tl.y0, x0 = tl.x0;
 
   // halo tile: 1 KB pieces, chunk slot XOR-swizzled by the tile column
   {
     const i32x4 xrs = make_rsrc4(a.x, x_bytes);
     const unsigned lds0 = lds_addr_of(smem);
-    constexpr int NPX = (XR * XWP * 8 + 63) / 64;
 #pragma unroll
-    for (int j = 0; j < (NPX + 3) / 4; ++j) {
+    for (int j = 0; j < XPW; ++j) {
       const int k = wave + 4 * j;
       if (k < NPX) {
         const int i = k * 64 + lane, sl = i & 7, p = i >> 3;
@@ -402,7 +491,7 @@ __global__ __launch_bounds__(256, 2) void lk_conv_rows_kernel(const srk_conv_arg
     for (int kh = 0; kh < K; ++kh)
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) {
-        const i32x4 b = lds_read16(xr + kh * (XWP * 128) + (((2 * ks + g) ^ swz(u)) << 4));
+        const i32x4 b = lds_read16(xr + kh * C::Halo::ROWB + (((2 * ks + g) ^ swz(u)) << 4));
         acc = Tr::mma(wf[kh * 4 + ks], b, acc);
       }
 #pragma unroll
@@ -446,22 +535,21 @@ __global__ __launch_bounds__(256) void lk_wgrad_packed_kernel(const srk_wgrad_ar
                                                               unsigned x_bytes, unsigned dy_bytes) {
   typedef DTraits<DT> Tr;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int XW = 16 + K - 1, XWP = (XW + 1) & ~1;
-  constexpr int xbuf = 16 * XWP * 128, dbuf = 16 * 16 * 32, buf = xbuf + dbuf;
-  constexpr int DTW = 16 + 2 * (K - 1) + 16, DTP = DTW * 2;      // plane row: columns -(K-1) .. 16 + (K-1) + 15, two bytes each
-  constexpr int NPL = 8;                                          // planes: <= 6 real + the zero plane (index cr)
-  constexpr int dt_bytes = NPL * 16 * DTP;
-  char* const DTb = smem + 2 * buf;
-  float* const red = reinterpret_cast<float*>(DTb + dt_bytes);    // 2 x 16 x 64 floats: the s = 1 waves' sums
+  typedef LkPackedCfg<K> C;
+  typedef typename C::Planes PL;
+  constexpr int XW = C::Halo::XW, XWP = C::Halo::XWP, ROWB = C::Halo::ROWB, xbuf = C::D_OFF, buf = C::BUF, DTP = PL::DTP;
+  char* const DTb = smem + C::DT_OFF;
+  float* const red = reinterpret_cast<float*>(smem + C::RED_OFF);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int slot = blockIdx.x, kh = blockIdx.y;
   const int H = a.H, W = a.W, P = K / 2, cr = a.cout_real;
-  const int t0 = slot * tq + min(slot, trem), nt = tq + (slot < trem ? 1 : 0);
+  const LkRange rg = lk_slot_range(slot, tq, trem);
+  const int t0 = rg.t0, nt = rg.nt;
   const i32x4 xrs = make_rsrc4(a.x, x_bytes), drs = make_rsrc4(a.dy, dy_bytes);
   const unsigned lds0 = lds_addr_of(smem);
 
-  constexpr int NPX = 16 * XWP * 8 / 64, XPW = (NPX + 3) / 4, DPW = 2;          // + 8 gradient pieces (two per wave)
+  constexpr int NPX = C::Halo::NPX, XPW = C::Halo::XPW, DPW = C::ND / 4;          // + 8 gradient pieces (two per wave)
   int xdesc[XPW], ddesc[DPW];
 #pragma unroll
   for (int j = 0; j < XPW; ++j) {
@@ -475,12 +563,8 @@ __global__ __launch_bounds__(256) void lk_wgrad_packed_kernel(const srk_wgrad_ar
     ddesc[j] = (pp >> 4) | ((pp & 15) << 8) | (c << 16) | ((c * 8 < a.Cout) ? 1 << 24 : 0);
   }
   auto dma_tile = [&](int tile, int b) {
-    int pt = tile;
-    const int tX = pt % tilesX;
-    pt /= tilesX;
-    const int tY = pt % tilesY;
-    const int n = pt / tilesY;
-    const int y0 = tY * 16, x0 = tX * 16;
+    const LkTile t = lk_tile_of(tile, tilesX, tilesY, C::TH);
+    const int n = t.n, y0 = t.y0, x0 = t.x0;
 #pragma unroll
     for (int j = 0; j < XPW; ++j) {
       const int k = wave + 4 * j;
@@ -500,22 +584,18 @@ __global__ __launch_bounds__(256) void lk_wgrad_packed_kernel(const srk_wgrad_ar
       dma16_hidden(drs, voff, (unsigned)__builtin_amdgcn_readfirstlane((int)(lds0 + b * buf + xbuf + (k << 10))));
     }
   };
-
-  // zero the planes once: the pad columns and the zero plane are never written again
-  for (int i = tid; i < dt_bytes / 16; i += 256) lds_write16(DTb + i * 16, i32x4{0, 0, 0, 0});
+  for (int i = tid; i < PL::BYTES / 16; i += 256) lds_write16(DTb + i * 16, i32x4{0, 0, 0, 0});
 
   const int s = wave >> 1, rb = wave & 1;                         // column block (halo columns 16 s ..), channel block
   int aoff[2];
 #pragma unroll
   for (int rd = 0; rd < 2; ++rd) aoff[rd] = tr_lane_off(16 * s, rd, rb, lane);
-  // B operand: lane (n = lane & 31 -> (kw, co), g = lane >> 5) reads gradient columns 16 s + 8 g - kw + j, j = 0..7, of plane co
   const int nn = lane & 31, kwn = nn / cr, con = nn - kwn * cr;
   const int plane = kwn < K ? con : cr;                           // columns beyond K * cr: the zero plane
-  const int boff = plane * 16 * DTP + (16 * s + 8 * (lane >> 5) - (kwn < K ? kwn : 0) + (K - 1)) * 2;
-  // transposition pass: thread = pixel (ty, tx) of the gradient tile
+  const int boff = plane * PL::PLANE + (16 * s + 8 * (lane >> 5) - (kwn < K ? kwn : 0) + (K - 1)) * 2;
   const int ty = tid >> 4, tx = tid & 15;
   const bool do_bias = a.dbp != nullptr && kh == 0;
-  float dbs[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  float dbs[C::MAXC] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 
   f32x16 acc;
 #pragma unroll
@@ -533,14 +613,14 @@ __global__ __launch_bounds__(256) void lk_wgrad_packed_kernel(const srk_wgrad_ar
       for (int c = 0; c < 6; ++c)
         if (c < cr) {
           const uint16_t hv = (uint16_t)(w4[c >> 1] >> ((c & 1) * 16));
-          *reinterpret_cast<uint16_t*>(DTb + (c * 16 + ty) * DTP + (tx + K - 1) * 2) = hv;
+          *reinterpret_cast<uint16_t*>(DTb + (c * PL::TH + ty) * DTP + (tx + K - 1) * 2) = hv;
           if (do_bias) dbs[c] += Tr::to_f32(hv);
         }
     }
     __syncthreads();
 #pragma unroll 4
     for (int y = 0; y < 16; ++y) {
-      const i32x4 af = tr_read2(X + y * (XWP * 128) + aoff[0], X + y * (XWP * 128) + aoff[1]);
+      const i32x4 af = tr_read2(X + y * ROWB + aoff[0], X + y * ROWB + aoff[1]);
       const uint16_t* bp = reinterpret_cast<const uint16_t*>(DTb + boff + y * DTP);
       i32x4 bf;
       bf.x = (int)((uint32_t)bp[0] | ((uint32_t)bp[1] << 16));
@@ -581,9 +661,7 @@ __global__ __launch_bounds__(256) void lk_wgrad_packed_kernel(const srk_wgrad_ar
       if (ci < a.Cin) sl[((size_t)kwn * a.Cin + ci) * a.Cout + con] = acc[e] + red[(rb * 16 + e) * 64 + lane];
     }
   }
-  // the stored channels that are padding: zeros (the finalize step adds whole slabs)
-  for (int i = tid; i < K * a.Cin * a.Cout; i += 256)
-    if (i % a.Cout >= cr) sl[i] = 0.f;
+  lk_few_zero_pad(sl, K * a.Cin * a.Cout, a.Cout, cr, tid);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -592,29 +670,25 @@ __global__ __launch_bounds__(256) void lk_wgrad_packed_kernel(const srk_wgrad_ar
 // SRResNet's 9x9 tail at 16 x 192 x 192).  K accumulators per wave; slabs are COMPACT: [tap][ci][4] (cout_real <= 4), one per
 // workgroup (srk_wgrad_slab_cout tells the caller).
 // ------------------------------------------------------------------------------------------------------------------
-constexpr int LK_TR = 8, LK_CS = 4;
 template <int DT, int K>
 __global__ __launch_bounds__(256) void lk_wgrad_allrows_kernel(const srk_wgrad_args a, int tilesX, int tilesY, int ntiles, int tq, int trem,
                                                                unsigned x_bytes, unsigned dy_bytes) {
   typedef DTraits<DT> Tr;
+  typedef LkAllRowsCfg<K> C;
+  typedef typename C::Planes PL;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int TR = LK_TR, CS = LK_CS;
-  constexpr int XW = 16 + K - 1, XWP = (XW + 1) & ~1, XR = TR + K - 1;
-  constexpr int xbuf = (XR * XWP * 128 + 1023) & ~1023, dbuf = TR * 16 * 32, buf = xbuf + dbuf;     // whole 1 KB DMA pieces
-  constexpr int DTW = 16 + 2 * (K - 1) + 16, DTP = DTW * 2;
-  constexpr int NPL = 8;
-  constexpr int dt_bytes = NPL * TR * DTP;
-  static_assert(K * 2 * 16 * 64 * 4 <= 2 * buf, "the final reduction reuses the tile buffers");
-  char* const DTb = smem + 2 * buf;
+  constexpr int TR = C::TH, CS = C::CS, XR = C::Halo::ROWS, XW = C::Halo::XW, XWP = C::Halo::XWP, ROWB = C::Halo::ROWB, xbuf = C::D_OFF, buf = C::BUF, DTP = PL::DTP;
+  char* const DTb = smem + C::DT_OFF;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int slot = blockIdx.x;
   const int H = a.H, W = a.W, P = K / 2, cr = a.cout_real;
-  const int t0 = slot * tq + min(slot, trem), nt = tq + (slot < trem ? 1 : 0);
+  const LkRange rg = lk_slot_range(slot, tq, trem);
+  const int t0 = rg.t0, nt = rg.nt;
   const i32x4 xrs = make_rsrc4(a.x, x_bytes), drs = make_rsrc4(a.dy, dy_bytes);
   const unsigned lds0 = lds_addr_of(smem);
 
-  constexpr int NPX = (XR * XWP * 8 + 63) / 64, XPW = (NPX + 3) / 4;      // + 4 gradient pieces (one per wave)
+  constexpr int NPX = C::Halo::NPX, XPW = C::Halo::XPW;      // + 4 gradient pieces (one per wave)
   int xdesc[XPW], ddesc;
 #pragma unroll
   for (int j = 0; j < XPW; ++j) {
@@ -627,12 +701,8 @@ __global__ __launch_bounds__(256) void lk_wgrad_allrows_kernel(const srk_wgrad_a
     ddesc = (pp >> 4) | ((pp & 15) << 8) | (c << 16) | ((c * 8 < a.Cout) ? 1 << 24 : 0);
   }
   auto dma_tile = [&](int tile, int b) {
-    int pt = tile;
-    const int tX = pt % tilesX;
-    pt /= tilesX;
-    const int tY = pt % tilesY;
-    const int n = pt / tilesY;
-    const int y0 = tY * TR, x0 = tX * 16;
+    const LkTile t = lk_tile_of(tile, tilesX, tilesY, C::TH);
+    const int n = t.n, y0 = t.y0, x0 = t.x0;
 #pragma unroll
     for (int j = 0; j < XPW; ++j) {
       const int k = wave + 4 * j;
@@ -650,8 +720,7 @@ __global__ __launch_bounds__(256) void lk_wgrad_allrows_kernel(const srk_wgrad_a
       dma16_hidden(drs, voff, (unsigned)__builtin_amdgcn_readfirstlane((int)(lds0 + b * buf + xbuf + (wave << 10))));
     }
   };
-
-  for (int i = tid; i < dt_bytes / 16; i += 256) lds_write16(DTb + i * 16, i32x4{0, 0, 0, 0});
+  for (int i = tid; i < PL::BYTES / 16; i += 256) lds_write16(DTb + i * 16, i32x4{0, 0, 0, 0});
 
   const int s = wave >> 1, rb = wave & 1;
   int aoff[2];
@@ -659,10 +728,10 @@ __global__ __launch_bounds__(256) void lk_wgrad_allrows_kernel(const srk_wgrad_a
   for (int rd = 0; rd < 2; ++rd) aoff[rd] = tr_lane_off(16 * s, rd, rb, lane);
   const int nn = lane & 31, kwn = nn / cr, con = nn - kwn * cr;
   const int plane = kwn < K ? con : cr;
-  const int boff = plane * TR * DTP + (16 * s + 8 * (lane >> 5) - (kwn < K ? kwn : 0) + (K - 1)) * 2;
+  const int boff = plane * PL::PLANE + (16 * s + 8 * (lane >> 5) - (kwn < K ? kwn : 0) + (K - 1)) * 2;
   const int ty = tid >> 4, tx = tid & 15;                          // transposition pass: threads 0 .. 127 = the tile's pixels
   const bool do_bias = a.dbp != nullptr;
-  float dbs[4] = {0.f, 0.f, 0.f, 0.f};
+  float dbs[CS] = {0.f, 0.f, 0.f, 0.f};
 
   f32x16 acc[K];
 #pragma unroll
@@ -697,7 +766,7 @@ __global__ __launch_bounds__(256) void lk_wgrad_allrows_kernel(const srk_wgrad_a
       bf.w = (int)((uint32_t)bp[6] | ((uint32_t)bp[7] << 16));
 #pragma unroll
       for (int kh = 0; kh < K; ++kh) {
-        const char* xr = X + (y + kh) * (XWP * 128);
+        const char* xr = X + (y + kh) * ROWB;
         const i32x4 af = tr_read2(xr + aoff[0], xr + aoff[1]);
         acc[kh] = Tr::mma(af, bf, acc[kh]);
       }
@@ -738,11 +807,9 @@ __global__ __launch_bounds__(256) void lk_wgrad_allrows_kernel(const srk_wgrad_a
         if (ci < a.Cin) sl[(((size_t)kh * K + kwn) * a.Cin + ci) * CS + con] = acc[kh][e] + red[((kh * 2 + rb) * 16 + e) * 64 + lane];
       }
   }
-  for (int i = tid; i < K * K * a.Cin * CS; i += 256)
-    if ((i & (CS - 1)) >= cr) sl[i] = 0.f;
+  lk_few_zero_pad(sl, K * K * a.Cin * CS, CS, cr, tid);
 }
 
-// whether the all-rows form takes this weight gradient (and its slabs are the compact [tap][ci][4] ones)
 // ---- 5x5 forward, 64 input -> <= 16 stored output channels, fp32 NCHW store behind PixelShuffle(2): the collapsed HR stage -------------
 // (hr_tail.hip: the image = one 5x5 conv of the upsampler's input.)  lk_conv_kernel gives every 16 x 16 tile its own workgroup and streams
 // the weights per kernel row: one workgroup per CU (91 KB of LDS), nothing of tile t + 1 overlaps tile t -- 375 us at 256 x 96 x 96 for
@@ -753,18 +820,18 @@ __global__ __launch_bounds__(256) void lk_wgrad_allrows_kernel(const srk_wgrad_a
 template <int DT>
 __global__ __launch_bounds__(256) void lk5_fwd_kernel(const srk_conv_args a, int tilesX, int tilesY, int tq, int trem, unsigned x_bytes) {
   typedef DTraits<DT> Tr;
-  constexpr int XT = 20, XB = XT * XT * 128, WB = 25 * 8 * 16 * 16;      // halo tile 51,200 B; compact weights 51,200 B
-  constexpr int NPC = XB / 1024;                                         // 50 pieces of 1 KB per halo tile
+  typedef Lk5FwdCfg C;
+  constexpr int XT = C::XT, XB = C::XB, WB = C::WB, NPC = C::NPC;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* const Wl = smem;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = lane & 31, h = lane >> 5;
   const int H = a.H, W = a.W;
-  const int slot = blockIdx.x;
-  const int t0 = slot * tq + min(slot, trem), nt = tq + (slot < trem ? 1 : 0);
+  const LkRange rg = lk_slot_range(blockIdx.x, tq, trem);
+  const int t0 = rg.t0, nt = rg.nt;
   if (nt <= 0) return;
-  const i32x4 xrsrc = make_rsrc4(a.x, x_bytes), wrsrc = make_rsrc4(a.wpk, 25u * 8u * 32u * 16u);
+  const i32x4 xrsrc = make_rsrc4(a.x, x_bytes), wrsrc = make_rsrc4(a.wpk, (unsigned)C::W_SRC_BYTES);
   const unsigned lds0 = lds_addr_of(smem);
 
   // bias -> registers first (the vector-memory counter retires in order: nothing hidden may be queued in front of a visible load)
@@ -799,16 +866,9 @@ __global__ __launch_bounds__(256) void lk5_fwd_kernel(const srk_conv_args a, int
     hconst[m] = (((iy - 2) * W + (ix - 2)) * a.x_pitch + a.x_coff + c * 8) * 2;
     hyx[m] = ((iy - 2) & 0xffff) | ((ix - 2) << 16);
   }
-  auto tile_of = [&](int t, int& n, int& y0, int& x0) {
-    int pt = t0 + t;
-    const int tX = pt % tilesX;
-    pt /= tilesX;
-    const int tY = pt % tilesY;
-    n = pt / tilesY; y0 = tY * 16; x0 = tX * 16;
-  };
   auto dma_tile = [&](int t, int b) {
-    int n, y0, x0;
-    tile_of(t, n, y0, x0);
+    const LkTile tl = lk_tile_of(t0 + t, tilesX, tilesY, C::TH);
+    const int n = tl.n, y0 = tl.y0, x0 = tl.x0;
     const int tbase = ((n * H + y0) * W + x0) * a.x_pitch * 2;
 #pragma unroll
     for (int m = 0; m < NPW; ++m) {
@@ -868,8 +928,8 @@ __global__ __launch_bounds__(256) void lk5_fwd_kernel(const srk_conv_args a, int
     // fp32 NCHW behind PixelShuffle(2): channel k = o*4 + i*2 + j of pixel (gy, gx) -> out[n][o][2 gy + i][2 gx + j] (+ post_add[o]); the h = 0
     // lanes hold the stored channels (register index = channel); a lane's (j = 0, 1) pair is one 8-byte store
     {
-      int n, y0, x0;
-      tile_of(t, n, y0, x0);
+      const LkTile tl = lk_tile_of(t0 + t, tilesX, tilesY, C::TH);
+      const int n = tl.n, y0 = tl.y0, x0 = tl.x0;
 #pragma unroll
       for (int pb = 0; pb < 2; ++pb) {
         const int gy = y0 + prow[pb], gx = x0 + px;
@@ -909,14 +969,14 @@ __global__ __launch_bounds__(256) void lk5_fwd_kernel(const srk_conv_args a, int
 template <int DT, int NW>
 __global__ __launch_bounds__(NW * 64) void lk5_rows_fwd_kernel(const srk_conv_args a, int nb, int segs, int seg_rows, int units, unsigned x_bytes) {
   typedef DTraits<DT> Tr;
-  constexpr int AHEAD = NW == 4 ? 2 : 1, PRO = NW + 4 + (AHEAD - 1) * NW, RING = PRO + NW;
-  constexpr int ROWB = 32 * 128, SP = 68, SCR = 32 * SP * 4;      // ring row 4,096 B; scratch [column][row], pitch 68 floats: 8,704 B per wave
+  typedef Lk5RowsCfg<NW> C;
+  constexpr int AHEAD = C::AHEAD, PRO = C::PRO, RING = C::RING, ROWB = C::ROWB, SP = C::SP, SCR = C::SCR;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = lane & 31, h = lane >> 5;
   const int H = a.H, W = a.W, O = a.Cout >> 2;
-  float* const scr = reinterpret_cast<float*>(smem + RING * ROWB + wave * SCR);
+  float* const scr = reinterpret_cast<float*>(smem + C::SCR_OFF + wave * SCR);
   const unsigned lds0 = lds_addr_of(smem);
   const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.wpk), 0, 25 * 8 * 32 * 16, 0x00020000);
   const i32x4 xrsrc = make_rsrc4(a.x, x_bytes);
@@ -962,8 +1022,8 @@ __global__ __launch_bounds__(NW * 64) void lk5_rows_fwd_kernel(const srk_conv_ar
 
   for (int u = blockIdx.x; u < units; u += gridDim.x) {
     const int sgm = u % segs, bb = (u / segs) % nb, n = u / (segs * nb);
-    const int x0 = bb * 28, ys = sgm * seg_rows;
-    const int ye = min(H, ys + seg_rows), nx = min(28, W - x0);
+    const int x0 = bb * C::BAND, ys = sgm * seg_rows;
+    const int ye = min(H, ys + seg_rows), nx = min(C::BAND, W - x0);
     const int steps = (ye - ys + NW - 1) / NW, qmax = (ye - ys) + 4;      // input rows q = 0 .. qmax - 1 <-> image rows ys - 2 + q
     auto dma_row = [&](int q) {                                       // wave-uniform q; ALWAYS four operations (the counted waits rely on it):
       const int gy = ys - 2 + q;                                      // rows behind the segment's last land as zeros in a free slot
@@ -1076,7 +1136,7 @@ template <int DT>
 __global__ __launch_bounds__(256) void lk5_dgrad_kernel(const srk_conv_args a, int nb, int segs, int seg_rows, int units, unsigned x_bytes) {
   typedef DTraits<DT> Tr;
   typedef typename Tr::elem elem;
-  constexpr int RING = 16, ROWB = 36 * 32;               // ring row: 36 pixels x 32 bytes = 72 chunks
+  constexpr int RING = Lk5DgradCfg::RING, ROWB = Lk5DgradCfg::ROWB;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1102,7 +1162,7 @@ __global__ __launch_bounds__(256) void lk5_dgrad_kernel(const srk_conv_args a, i
   const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(a.out, 0, 0x7fffffff, 0x00020000);
   for (int u = blockIdx.x; u < units; u += gridDim.x) {
     const int sgm = u % segs, bb = (u / segs) % nb, n = u / (segs * nb);
-    const int x0 = bb * 32, ys = sgm * seg_rows;
+    const int x0 = bb * Lk5DgradCfg::BAND, ys = sgm * seg_rows;
     const int ye = min(H, ys + seg_rows);
     const int steps = (ye - ys + 3) >> 2, qmax = (ye - ys) + 4;      // input rows q = 0 .. qmax - 1 <-> image rows ys - 2 + q
     auto dma_row = [&](int q) {                                       // wave-uniform q; ALWAYS two operations (the counted waits rely on it)
@@ -1235,13 +1295,15 @@ template <int DT>
 __global__ __launch_bounds__(256) void lk5_wgrad_kernel(const srk_wgrad_args a, int tilesX, int tilesY, int tq, int trem,
                                                         unsigned x_bytes, unsigned dy_bytes) {
   typedef DTraits<DT> Tr;
-  constexpr int XB = 16 * 16 * 128, DP = 20, DB = 13 * 1024, BUF = XB + DB;      // gradient halo: 20 x 20 x 32 B = 12,800 (+ DMA slack)
+  typedef Lk5WgradCfg C;
+  constexpr int XB = C::XB, DP = C::DP, BUF = C::BUF;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int slot = blockIdx.x;
   const int H = a.H, W = a.W;
-  const int t0 = slot * tq + min(slot, trem), nt = tq + (slot < trem ? 1 : 0);
+  const LkRange rg = lk_slot_range(slot, tq, trem);
+  const int t0 = rg.t0, nt = rg.nt;
   const i32x4 xrs = make_rsrc4(a.x, x_bytes), drs = make_rsrc4(a.dy, dy_bytes);
   const unsigned lds0 = lds_addr_of(smem);
 
@@ -1264,12 +1326,8 @@ __global__ __launch_bounds__(256) void lk5_wgrad_kernel(const srk_wgrad_args a, 
   // a tile's DMA is 12 pieces per wave (8 of x, up to 4 of the gradient halo); piece p of tile `t` into buffer b
   struct TileAt { int y0, x0, xbase, dbase; };
   auto tile_at = [&](int tile) {
-    int pt = tile;
-    const int tX = pt % tilesX;
-    pt /= tilesX;
-    const int tY = pt % tilesY;
-    const int n = pt / tilesY;
-    const int y0 = tY * 16, x0 = tX * 16;
+    const LkTile tl = lk_tile_of(tile, tilesX, tilesY, C::TH);
+    const int n = tl.n, y0 = tl.y0, x0 = tl.x0;
     return TileAt{y0, x0, ((n * H + y0) * W + x0) * a.x_pitch * 2, ((n * H + y0) * W + x0) * a.dy_pitch * 2};
   };
   auto dma_piece = [&](const TileAt& t, int b, int p) {
@@ -1443,30 +1501,137 @@ __global__ __launch_bounds__(256) void lk5_wgrad_kernel(const srk_wgrad_args a, 
   }
 }
 
+// ---- host ------------------------------------------------------------------------------------------------------------------------
+int lk_cus() { static const int cus = [] { int c = srk_device_cus(); return c > 0 ? c : 256; }(); return cus; }
+// the launchers below are L<DT>::launch / L<DT, K>::launch: the instantiation for a call's dtype, and for its kernel size 5 / 7 / 9
+template <template <int> class L, class A> int lk_by_dtype(const A& a, hipStream_t st) {
+  return a.dtype == SRK_BF16 ? L<SRK_BF16>::launch(a, st) : L<SRK_F16>::launch(a, st);
+}
+template <template <int, int> class L, int DT, class A> int lk_by_k(const A& a, hipStream_t st) {
+  return a.KH == 5 ? L<DT, 5>::launch(a, st) : a.KH == 7 ? L<DT, 7>::launch(a, st) : L<DT, 9>::launch(a, st);
+}
+template <template <int, int> class L, class A> int lk_by_dtype_k(const A& a, hipStream_t st) {
+  return a.dtype == SRK_BF16 ? lk_by_k<L, SRK_BF16>(a, st) : lk_by_k<L, SRK_F16>(a, st);
+}
+// one launch: once per kernel its dynamic-LDS limit (RESERVE bytes; 0: the default limit holds), then srk_last_kernel()'s name and the launch
+template <auto KERNEL, int RESERVE, class... T> int lk_launch(const char* name, const char* no_lds, dim3 grid, int threads, int lds, hipStream_t st, T... args) {
+  static_assert(RESERVE <= LK_LDS_MAX, "LDS");
+  static const hipError_t attr = RESERVE ? hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, RESERVE) : hipSuccess;
+  if (attr != hipSuccess) { srk_set_error(no_lds); return (int)attr; }
+  srk_kernel_name = name;
+  hipLaunchKernelGGL(KERNEL, grid, dim3(threads), lds, st, args...);
+  SRK_LAUNCH_CHECK();
+  return 0;
+}
+template <class A> unsigned lk_bytes(const A& a, int pitch) { return (unsigned)((long long)a.N * a.H * a.W * pitch * 2); }
+// The walk of lk5_rows_fwd_kernel and lk5_dgrad_kernel: bands of band_w columns, each cut into row segments = units.  As many units as
+// there are CUs at small batches, but not more (a second round of units doubles the launch; a segment re-reads four halo rows), at
+// least 8 rows each, whole steps of row_quantum rows.
+struct LkBandUnits { int nb, segs, seg_rows; long long units; int grid; };
+LkBandUnits lk_band_units(int N, int H, int W, int band_w, int row_quantum) {
+  const int cus = lk_cus(), nb = (W + band_w - 1) / band_w;
+  int segs = (int)(cus / ((long long)N * nb));
+  const int max_segs = (H + 7) / 8;
+  if (segs > max_segs) segs = max_segs;
+  if (segs < 1) segs = 1;
+  const int seg_rows = (((H + segs - 1) / segs) + row_quantum - 1) / row_quantum * row_quantum;
+  segs = (H + seg_rows - 1) / seg_rows;
+  const long long units = (long long)N * nb * segs;
+  return LkBandUnits{nb, segs, seg_rows, units, (int)(units < cus ? units : cus)};
+}
+
 bool lk5_wgrad_ok(const srk_wgrad_args& a) {
   static const bool off = [] { const char* e = srk_dbg_getenv("SRK_NO_LK5"); return e && e[0] == '1'; }();      // A/B knob
   return !off && a.KH == 5 && a.Cin == 64 && a.Cout == 16 && (a.cout_real == 0 || a.cout_real > 6) && a.x_pitch % 8 == 0 && a.dy_pitch % 8 == 0 &&
          a.x_coff % 8 == 0 && a.dy_coff % 8 == 0;
 }
-
+// whether the all-rows form takes this weight gradient (and its slabs are the compact [tap][ci][CS] ones)
 bool lk_all_rows(const srk_wgrad_args& a) {
   static const bool off = [] { const char* e = srk_dbg_getenv("SRK_NO_LK_ALLROWS"); const char* p = srk_dbg_getenv("SRK_NO_LK_PACKED"); return (e && e[0] == '1') || (p && p[0] == '1'); }();
-  return !off && a.cout_real > 0 && a.cout_real <= LK_CS && a.cout_real * a.KW <= 32 && a.KH >= 5;
+  return !off && a.cout_real > 0 && a.cout_real <= LkAllRowsCfg<5>::CS && a.cout_real * a.KW <= 32 && a.KH >= 5;
 }
-
-int lk_wgrad_slabs_for(const srk_wgrad_args& a) {
-  static const int cus = [] { int c = srk_device_cus(); return c > 0 ? c : 256; }();
-  if (lk_all_rows(a)) {                        // one workgroup per slab, all kernel rows inside
-    const long long nt8 = (long long)a.N * ((a.H + LK_TR - 1) / LK_TR) * ((a.W + 15) / 16);
-    return (int)(nt8 < cus ? nt8 : cus);
+// srk_last_kernel() names that carry the kernel size: prefix + "5>" / "7>" / "9>"
+#define LK_NAME_K(prefix) (K == 5 ? prefix "5>" : K == 7 ? prefix "7>" : prefix "9>")
+constexpr const char* LK_NO_LDS = "srk_conv2d: cannot reserve LDS for the large-kernel conv";
+constexpr const char* LK5_NO_LDS = "srk_conv2d: cannot reserve LDS for the 5x5 image conv";
+// the two kernels that give every tile of C a workgroup; w_bytes: their last argument
+template <auto KERNEL, class C, int RESERVE> int lk_tile_launch(const char* name, const srk_conv_args& a, unsigned w_bytes, hipStream_t st) {
+  const long long nb = C::tiles(a.N, a.H, a.W);
+  SRK_CHECK_ARG(nb <= 0x7fffffffLL, "srk_conv2d: %lld workgroups", nb);
+  return lk_launch<KERNEL, RESERVE>(name, LK_NO_LDS, dim3((unsigned)nb), 256, C::LDS_BYTES, st, a, C::tiles_x(a.W), C::tiles_y(a.H), lk_bytes(a, a.x_pitch), w_bytes);
+}
+template <int DT, int CPP, int NRB, int K> struct LkConvLaunch {
+  typedef LkConvCfg<CPP, NRB, K> C;
+  static_assert(C::LDS_BYTES <= LK_LDS_MAX, "LkConvCfg: LDS");
+  static_assert((CPP == 2 && NRB == 2) || (CPP == 8 && NRB == 1), "name below");
+  static int launch(const srk_conv_args& a, hipStream_t st) {
+    return lk_tile_launch<&lk_conv_kernel<DT, CPP, NRB, K>, C, LK_LDS_MAX>(CPP == 2 ? LK_NAME_K("lk_conv<2,2,") : LK_NAME_K("lk_conv<8,1,"), a, (unsigned)C::W_BYTES, st);
   }
-  const long long ntiles = (long long)a.N * ((a.H + 15) / 16) * ((a.W + 15) / 16);
-  if (lk5_wgrad_ok(a)) return (int)(ntiles < cus ? ntiles : cus);      // one workgroup per slab, all 25 taps inside
-  long long s = cus / a.KH;
-  if (s < 1) s = 1;
-  if (s > ntiles) s = ntiles;
-  return (int)s;
+};
+template <int DT, int K> struct LkConvFwdLaunch : LkConvLaunch<DT, 8, 1, K> {};      // 64 input channels, <= 32 output rows
+template <int DT, int K> struct LkConvBwdLaunch : LkConvLaunch<DT, 2, 2, K> {};      // 16 stored gradient channels, 64 rows
+template <int DT, int K> struct LkRowsLaunch {
+  typedef LkRowsCfg<K> C;
+  static_assert(C::LDS_BYTES <= 80 * 1024, "LkRowsCfg: two workgroups per CU");
+  static int launch(const srk_conv_args& a, hipStream_t st) {
+    return lk_tile_launch<&lk_conv_rows_kernel<DT, K>, C, C::LDS_BYTES>(LK_NAME_K("lk_conv_rows<"), a, (unsigned)((long long)K * K * 64 * a.CoutP * 2), st);
+  }
+};
+// the two band walkers: C::NW waves, one unit of lk_band_units after the other
+template <auto KERNEL, class C, int RESERVE> int lk_band_launch(const char* name, const srk_conv_args& a, hipStream_t st) {
+  const LkBandUnits u = lk_band_units(a.N, a.H, a.W, C::BAND, C::NW);
+  SRK_CHECK_ARG(u.units <= 0x7fffffffLL, "srk_conv2d: %lld units", u.units);
+  return lk_launch<KERNEL, RESERVE>(name, LK5_NO_LDS, dim3(u.grid), C::NW * 64, C::LDS_BYTES, st, a, u.nb, u.segs, u.seg_rows, (int)u.units, lk_bytes(a, a.x_pitch));
 }
+// (NW = 8 -- two waves per SIMD -- needs 160 weight + 64 accumulator + 24 fragment registers of a wave's 256: hipcc spills 83 of them, and a
+// scratch access is a vector-memory operation the hand-counted waits do not include.  One wave per SIMD it is.)
+template <int DT> struct Lk5RowsFwdLaunch {
+  typedef Lk5RowsCfg<4> C;
+  static int launch(const srk_conv_args& a, hipStream_t st) { return lk_band_launch<&lk5_rows_fwd_kernel<DT, C::NW>, C, C::LDS_BYTES>("lk5_rows_fwd", a, st); }
+};
+// the data gradient of the collapsed HR stage: 5x5, 16 stored channels -> 64, plain NHWC store
+bool lk5_dgrad_ok(const srk_conv_args& a) {
+  return a.KH == 5 && a.Cin == 16 && a.CoutP == 64 && a.Cout == 64 && a.out_mode == SRK_OUT_NHWC && !a.bias && !a.res && !a.relu && !a.mask &&
+         (SRK_LK5_STAMPS || !a.post_add) && a.scale == 1.f && (long long)a.N * a.H * a.W * a.out_pitch * 2 < 0x7fff0000LL;
+}
+template <int DT> struct Lk5DgradLaunch {
+  static_assert(Lk5DgradCfg::LDS_BYTES <= 64 * 1024, "Lk5DgradCfg: the default dynamic-LDS limit holds");
+  static int launch(const srk_conv_args& a, hipStream_t st) { return lk_band_launch<&lk5_dgrad_kernel<DT>, Lk5DgradCfg, 0>("lk5_dgrad", a, st); }
+};
+template <int DT> struct Lk5FwdLaunch {
+  static int launch(const srk_conv_args& a, hipStream_t st) {
+    typedef Lk5FwdCfg C;
+    static_assert(C::LDS_BYTES <= LK_LDS_MAX, "Lk5FwdCfg: LDS");
+    const long long ntiles = C::tiles(a.N, a.H, a.W);
+    SRK_CHECK_ARG(ntiles <= 0x7fffffffLL, "srk_conv2d: %lld tiles", ntiles);
+    const int slots = (int)(ntiles < lk_cus() ? ntiles : lk_cus());
+    return lk_launch<&lk5_fwd_kernel<DT>, LK_LDS_MAX>("lk5_fwd", LK5_NO_LDS, dim3(slots), 256, C::LDS_BYTES, st, a, C::tiles_x(a.W), C::tiles_y(a.H), (int)(ntiles / slots),
+                                                       (int)(ntiles % slots), lk_bytes(a, a.x_pitch));
+  }
+};
+// The weight gradients: a.nslabs workgroups (x GRID_Y kernel rows where a workgroup owns one), each a contiguous range of C's tiles: tq of
+// them, the first trem workgroups one more (lk_slot_range).  NTILES: the kernel takes the tile count as well.
+template <auto KERNEL, class C, int GRID_Y, bool NTILES> int lk_wgrad_launch(const char* name, const srk_wgrad_args& a, hipStream_t st) {
+  static_assert(C::LDS_BYTES <= LK_LDS_MAX, "the Cfg's LDS");
+  constexpr const char* no_lds = "srk_conv2d_wgrad: cannot reserve LDS";
+  const long long nt = C::tiles(a.N, a.H, a.W);
+  const int slabs = a.nslabs, tX = C::tiles_x(a.W), tY = C::tiles_y(a.H), tq = (int)(nt / slabs), trem = (int)(nt % slabs);
+  const unsigned xb = lk_bytes(a, a.x_pitch), db = lk_bytes(a, a.dy_pitch);
+  if constexpr (NTILES) return lk_launch<KERNEL, LK_LDS_MAX>(name, no_lds, dim3(slabs, GRID_Y), 256, C::LDS_BYTES, st, a, tX, tY, (int)nt, tq, trem, xb, db);
+  else return lk_launch<KERNEL, LK_LDS_MAX>(name, no_lds, dim3(slabs, GRID_Y), 256, C::LDS_BYTES, st, a, tX, tY, tq, trem, xb, db);
+}
+template <int DT, int K> struct LkAllRowsLaunch {
+  static int launch(const srk_wgrad_args& a, hipStream_t st) { return lk_wgrad_launch<&lk_wgrad_allrows_kernel<DT, K>, LkAllRowsCfg<K>, 1, true>(LK_NAME_K("lk_wgrad_allrows<"), a, st); }
+};
+template <int DT> struct Lk5WgradLaunch {
+  static int launch(const srk_wgrad_args& a, hipStream_t st) { return lk_wgrad_launch<&lk5_wgrad_kernel<DT>, Lk5WgradCfg, 1, false>("lk5_wgrad", a, st); }
+};
+template <int DT, int K> struct LkPackedLaunch {
+  static int launch(const srk_wgrad_args& a, hipStream_t st) { return lk_wgrad_launch<&lk_wgrad_packed_kernel<DT, K>, LkPackedCfg<K>, K, true>(LK_NAME_K("lk_wgrad_packed<"), a, st); }
+};
+template <int DT, int K> struct LkWgradLaunch {
+  static int launch(const srk_wgrad_args& a, hipStream_t st) { return lk_wgrad_launch<&lk_wgrad_kernel<DT, K>, LkWgradCfg<K>, K, true>(LK_NAME_K("lk_wgrad<"), a, st); }
+};
 
 }  // namespace
 
@@ -1490,139 +1655,18 @@ bool srk_conv_lk_ok(const srk_conv_args& a) {
   return mx * 2 < 0x7fff0000LL;
 }
 
-// srk_last_kernel() names that carry the kernel size: prefix + "5>" / "7>" / "9>"
-#define LK_NAME_K(prefix) (K == 5 ? prefix "5>" : K == 7 ? prefix "7>" : prefix "9>")
-
-template <int DT, int CPP, int NRB, int K> static int lk_launch_k(const srk_conv_args& a, hipStream_t st) {
-  constexpr int XT = 16 + K - 1, XTP = (XT + 1) & ~1;
-  constexpr int xs = (XT * XTP * CPP * 16 + 1023) & ~1023, slab = K * CPP * 32 * NRB * 16;
-  constexpr int lds = xs + 2 * slab;
-  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&lk_conv_kernel<DT, CPP, NRB, K>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  if (attr != hipSuccess) { srk_set_error("srk_conv2d: cannot reserve LDS for the large-kernel conv"); return (int)attr; }
-  SRK_CHECK_ARG(lds <= 160 * 1024, "srk_conv2d: %dx%d kernel needs %d bytes of LDS", K, K, lds);
-  const int tilesX = (a.W + 15) / 16, tilesY = (a.H + 15) / 16;
-  const long long nb = (long long)a.N * tilesX * tilesY;
-  SRK_CHECK_ARG(nb <= 0x7fffffffLL, "srk_conv2d: %lld workgroups", nb);
-  static_assert((CPP == 2 && NRB == 2) || (CPP == 8 && NRB == 1), "name below");
-  srk_kernel_name = CPP == 2 ? LK_NAME_K("lk_conv<2,2,") : LK_NAME_K("lk_conv<8,1,");
-  hipLaunchKernelGGL((lk_conv_kernel<DT, CPP, NRB, K>), dim3((unsigned)nb), dim3(256), lds, st, a, tilesX, tilesY,
-                     (unsigned)((long long)a.N * a.H * a.W * a.x_pitch * 2), (unsigned)((long long)K * slab));
-  SRK_LAUNCH_CHECK();
-  return 0;
-}
-template <int DT, int CPP, int NRB> static int lk_launch(const srk_conv_args& a, hipStream_t st) {
-  switch (a.KH) {
-    case 5: return lk_launch_k<DT, CPP, NRB, 5>(a, st);
-    case 7: return lk_launch_k<DT, CPP, NRB, 7>(a, st);
-    default: return lk_launch_k<DT, CPP, NRB, 9>(a, st);
-  }
-}
-
-template <int DT, int K> static int lk_rows_launch_k(const srk_conv_args& a, hipStream_t st) {
-  constexpr int XWP = (16 + K - 1 + 1) & ~1, XR = 8 + K - 1;
-  constexpr int lds = ((XR * XWP * 128 + 1023) & ~1023) + 4 * 4096 + 4 * 512;
-  static_assert(lds <= 80 * 1024, "two workgroups per CU");
-  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&lk_conv_rows_kernel<DT, K>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  if (attr != hipSuccess) { srk_set_error("srk_conv2d: cannot reserve LDS for the large-kernel conv"); return (int)attr; }
-  const int tilesX = (a.W + 15) / 16, tilesY = (a.H + 7) / 8;
-  const long long nb = (long long)a.N * tilesX * tilesY;
-  SRK_CHECK_ARG(nb <= 0x7fffffffLL, "srk_conv2d: %lld workgroups", nb);
-  srk_kernel_name = LK_NAME_K("lk_conv_rows<");
-  hipLaunchKernelGGL((lk_conv_rows_kernel<DT, K>), dim3((unsigned)nb), dim3(256), lds, st, a, tilesX, tilesY,
-                     (unsigned)((long long)a.N * a.H * a.W * a.x_pitch * 2), (unsigned)((long long)K * K * 64 * a.CoutP * 2));
-  SRK_LAUNCH_CHECK();
-  return 0;
-}
-template <int DT> static int lk_rows_launch(const srk_conv_args& a, hipStream_t st) {
-  switch (a.KH) {
-    case 5: return lk_rows_launch_k<DT, 5>(a, st);
-    case 7: return lk_rows_launch_k<DT, 7>(a, st);
-    default: return lk_rows_launch_k<DT, 9>(a, st);
-  }
-}
-
-template <int DT, int NW> static int lk5_rows_fwd_launch_w(const srk_conv_args& a, hipStream_t st) {
-  constexpr int PRO = NW + 4 + (NW == 4 ? NW : 0), lds = (PRO + NW) * 32 * 128 + NW * 32 * 68 * 4;
-  static const int cus = [] { int c = srk_device_cus(); return c > 0 ? c : 256; }();
-  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&lk5_rows_fwd_kernel<DT, NW>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  if (attr != hipSuccess) { srk_set_error("srk_conv2d: cannot reserve LDS for the 5x5 image conv"); return (int)attr; }
-  const int nb = (a.W + 27) / 28;
-  // row segments per band: as many units as there are CUs at small batches, but not more (a second round of units doubles the launch;
-  // a segment re-reads four halo rows), at least 8 rows each
-  int segs = (int)(cus / ((long long)a.N * nb));
-  const int max_segs = (a.H + 7) / 8;
-  if (segs > max_segs) segs = max_segs;
-  if (segs < 1) segs = 1;
-  const int seg_rows = (((a.H + segs - 1) / segs) + NW - 1) / NW * NW;
-  segs = (a.H + seg_rows - 1) / seg_rows;
-  const long long units = (long long)a.N * nb * segs;
-  SRK_CHECK_ARG(units <= 0x7fffffffLL, "srk_conv2d: %lld units", units);
-  const int grid = (int)(units < cus ? units : cus);
-  srk_kernel_name = "lk5_rows_fwd";
-  hipLaunchKernelGGL((lk5_rows_fwd_kernel<DT, NW>), dim3(grid), dim3(NW * 64), lds, st, a, nb, segs, seg_rows, (int)units,
-                     (unsigned)((long long)a.N * a.H * a.W * a.x_pitch * 2));
-  SRK_LAUNCH_CHECK();
-  return 0;
-}
-// (NW = 8 -- two waves per SIMD -- needs 160 weight + 64 accumulator + 24 fragment registers of a wave's 256: hipcc spills 83 of them, and a
-// scratch access is a vector-memory operation the hand-counted waits do not include.  One wave per SIMD it is.)
-template <int DT> static int lk5_rows_fwd_launch(const srk_conv_args& a, hipStream_t st) { return lk5_rows_fwd_launch_w<DT, 4>(a, st); }
-
-// the data gradient of the collapsed HR stage: 5x5, 16 stored channels -> 64, plain NHWC store
-static bool lk5_dgrad_ok(const srk_conv_args& a) {
-  return a.KH == 5 && a.Cin == 16 && a.CoutP == 64 && a.Cout == 64 && a.out_mode == SRK_OUT_NHWC && !a.bias && !a.res && !a.relu && !a.mask &&
-         (SRK_LK5_STAMPS || !a.post_add) && a.scale == 1.f && (long long)a.N * a.H * a.W * a.out_pitch * 2 < 0x7fff0000LL;
-}
-template <int DT> static int lk5_dgrad_launch(const srk_conv_args& a, hipStream_t st) {
-  constexpr int lds = 16 * 36 * 32;
-  static const int cus = [] { int c = srk_device_cus(); return c > 0 ? c : 256; }();
-  const int nb = (a.W + 31) / 32;
-  int segs = (int)(cus / ((long long)a.N * nb));      // (as in lk5_rows_fwd_launch)
-  const int max_segs = (a.H + 7) / 8;
-  if (segs > max_segs) segs = max_segs;
-  if (segs < 1) segs = 1;
-  const int seg_rows = (((a.H + segs - 1) / segs) + 3) & ~3;
-  segs = (a.H + seg_rows - 1) / seg_rows;
-  const long long units = (long long)a.N * nb * segs;
-  SRK_CHECK_ARG(units <= 0x7fffffffLL, "srk_conv2d: %lld units", units);
-  const int grid = (int)(units < cus ? units : cus);
-  srk_kernel_name = "lk5_dgrad";
-  hipLaunchKernelGGL((lk5_dgrad_kernel<DT>), dim3(grid), dim3(256), lds, st, a, nb, segs, seg_rows, (int)units,
-                     (unsigned)((long long)a.N * a.H * a.W * a.x_pitch * 2));
-  SRK_LAUNCH_CHECK();
-  return 0;
-}
-
-template <int DT> static int lk5_fwd_launch(const srk_conv_args& a, hipStream_t st) {
-  constexpr int lds = 25 * 8 * 16 * 16 + 2 * 20 * 20 * 128;
-  static const int cus = [] { int c = srk_device_cus(); return c > 0 ? c : 256; }();
-  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&lk5_fwd_kernel<DT>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  if (attr != hipSuccess) { srk_set_error("srk_conv2d: cannot reserve LDS for the 5x5 image conv"); return (int)attr; }
-  const int tilesX = (a.W + 15) / 16, tilesY = (a.H + 15) / 16;
-  const long long ntiles = (long long)a.N * tilesX * tilesY;
-  SRK_CHECK_ARG(ntiles <= 0x7fffffffLL, "srk_conv2d: %lld tiles", ntiles);
-  const int slots = (int)(ntiles < cus ? ntiles : cus);
-  srk_kernel_name = "lk5_fwd";
-  hipLaunchKernelGGL((lk5_fwd_kernel<DT>), dim3(slots), dim3(256), lds, st, a, tilesX, tilesY, (int)(ntiles / slots), (int)(ntiles % slots),
-                     (unsigned)((long long)a.N * a.H * a.W * a.x_pitch * 2));
-  SRK_LAUNCH_CHECK();
-  return 0;
-}
-
 int srk_conv_lk_launch(const srk_conv_args& a, hipStream_t st) {
   static const bool no_lk5 = [] { const char* e = srk_dbg_getenv("SRK_NO_LK5"); return e && e[0] == '1'; }();      // A/B knob
   static const bool no_lk5_rows = [] { const char* e = srk_dbg_getenv("SRK_NO_LK5_ROWS"); return e && e[0] == '1'; }();      // A/B knob
-  if (a.out_mode == SRK_OUT_PLANAR && a.KH == 5 && !no_lk5 && !no_lk5_rows && a.Cout <= 12)
-    return a.dtype == SRK_BF16 ? lk5_rows_fwd_launch<SRK_BF16>(a, st) : lk5_rows_fwd_launch<SRK_F16>(a, st);
-  if (a.out_mode == SRK_OUT_PLANAR && a.KH == 5 && !no_lk5) return a.dtype == SRK_BF16 ? lk5_fwd_launch<SRK_BF16>(a, st) : lk5_fwd_launch<SRK_F16>(a, st);
+  if (a.out_mode == SRK_OUT_PLANAR && a.KH == 5 && !no_lk5 && !no_lk5_rows && a.Cout <= 12) return lk_by_dtype<Lk5RowsFwdLaunch>(a, st);
+  if (a.out_mode == SRK_OUT_PLANAR && a.KH == 5 && !no_lk5) return lk_by_dtype<Lk5FwdLaunch>(a, st);
   static const bool no_rows = [] { const char* e = srk_dbg_getenv("SRK_NO_LK_ROWS"); return e && e[0] == '1'; }();      // A/B knob
   if (!no_rows && a.out_mode == SRK_OUT_NHWC && a.Cin == 64 && a.cout_real > 0 && a.cout_real <= 4 && a.cout_real * a.KW <= 32 && a.Cout == 16 && !a.relu && !a.res && a.scale == 1.f)
-    return a.dtype == SRK_BF16 ? lk_rows_launch<SRK_BF16>(a, st) : lk_rows_launch<SRK_F16>(a, st);
+    return lk_by_dtype_k<LkRowsLaunch>(a, st);
   static const bool no_lk5_dgrad = [] { const char* e = srk_dbg_getenv("SRK_NO_LK5_DGRAD"); return e && e[0] == '1'; }();      // A/B knob
-  if (!no_lk5 && !no_lk5_dgrad && lk5_dgrad_ok(a)) return a.dtype == SRK_BF16 ? lk5_dgrad_launch<SRK_BF16>(a, st) : lk5_dgrad_launch<SRK_F16>(a, st);
-  if (a.Cin == 16) return a.dtype == SRK_BF16 ? lk_launch<SRK_BF16, 2, 2>(a, st) : lk_launch<SRK_F16, 2, 2>(a, st);
-  return a.dtype == SRK_BF16 ? lk_launch<SRK_BF16, 8, 1>(a, st) : lk_launch<SRK_F16, 8, 1>(a, st);
+  if (!no_lk5 && !no_lk5_dgrad && lk5_dgrad_ok(a)) return lk_by_dtype<Lk5DgradLaunch>(a, st);
+  if (a.Cin == 16) return lk_by_dtype_k<LkConvBwdLaunch>(a, st);
+  return lk_by_dtype_k<LkConvFwdLaunch>(a, st);
 }
 
 bool srk_wgrad_lk_ok(const srk_wgrad_args& a) {
@@ -1631,66 +1675,20 @@ bool srk_wgrad_lk_ok(const srk_wgrad_args& a) {
   const long long px = (long long)a.N * a.H * a.W;
   return px * a.x_pitch * 2 < 0x7fff0000LL && px * a.dy_pitch * 2 < 0x7fff0000LL;
 }
-int srk_wgrad_lk_slabs(const srk_wgrad_args& a) { return lk_wgrad_slabs_for(a); }
-int srk_wgrad_lk_slab_cout(const srk_wgrad_args& a) { return lk_all_rows(a) ? LK_CS : a.Cout; }
+int srk_wgrad_lk_slabs(const srk_wgrad_args& a) {
+  const long long cus = lk_cus(), ntiles = LkWgradCfg<5>::tiles(a.N, a.H, a.W), nt8 = LkAllRowsCfg<5>::tiles(a.N, a.H, a.W);
+  if (lk_all_rows(a)) return (int)(nt8 < cus ? nt8 : cus);             // one workgroup per slab, all kernel rows inside
+  if (lk5_wgrad_ok(a)) return (int)(ntiles < cus ? ntiles : cus);      // one workgroup per slab, all 25 taps inside
+  const long long s = cus / a.KH < 1 ? 1 : cus / a.KH;                 // K workgroups (one per kernel row) share a slab's tiles (lk_wgrad_packed_kernel's too)
+  return (int)(s > ntiles ? ntiles : s);
+}
+int srk_wgrad_lk_slab_cout(const srk_wgrad_args& a) { return lk_all_rows(a) ? LkAllRowsCfg<5>::CS : a.Cout; }
 
-template <int DT, int K> static int lk_wgrad_launch_k(const srk_wgrad_args& a, hipStream_t st) {
-  constexpr int XWP = (16 + K - 1 + 1) & ~1;
-  constexpr int lds = 2 * (16 * XWP * 128 + 16 * 16 * 32 + 1024);
-  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&lk_wgrad_kernel<DT, K>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  if (attr != hipSuccess) { srk_set_error("srk_conv2d_wgrad: cannot reserve LDS"); return (int)attr; }
-  const int tilesX = (a.W + 15) / 16, tilesY = (a.H + 15) / 16;
-  const long long ntiles = (long long)a.N * tilesX * tilesY;
-  const int slabs = a.nslabs;
-  const unsigned xb = (unsigned)((long long)a.N * a.H * a.W * a.x_pitch * 2), db = (unsigned)((long long)a.N * a.H * a.W * a.dy_pitch * 2);
-  if (lk_all_rows(a)) {
-    constexpr int XR = LK_TR + K - 1;
-    constexpr int alds = 2 * (((XR * XWP * 128 + 1023) & ~1023) + LK_TR * 16 * 32) + 8 * LK_TR * (16 + 2 * (K - 1) + 16) * 2;
-    static_assert(alds <= 160 * 1024, "LDS");
-    static const hipError_t aattr = hipFuncSetAttribute(reinterpret_cast<const void*>(&lk_wgrad_allrows_kernel<DT, K>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (aattr != hipSuccess) { srk_set_error("srk_conv2d_wgrad: cannot reserve LDS"); return (int)aattr; }
-    const int tY8 = (a.H + LK_TR - 1) / LK_TR;
-    const long long nt8 = (long long)a.N * tY8 * tilesX;
-    srk_kernel_name = LK_NAME_K("lk_wgrad_allrows<");
-    hipLaunchKernelGGL((lk_wgrad_allrows_kernel<DT, K>), dim3(slabs), dim3(256), alds, st, a, tilesX, tY8, (int)nt8, (int)(nt8 / slabs), (int)(nt8 % slabs), xb, db);
-    SRK_LAUNCH_CHECK();
-    return 0;
-  }
-  if constexpr (K == 5) {
-    if (lk5_wgrad_ok(a)) {
-      constexpr int l5 = 3 * (16 * 16 * 128 + 13 * 1024);
-      static const hipError_t a5 = hipFuncSetAttribute(reinterpret_cast<const void*>(&lk5_wgrad_kernel<DT>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (a5 != hipSuccess) { srk_set_error("srk_conv2d_wgrad: cannot reserve LDS"); return (int)a5; }
-      srk_kernel_name = "lk5_wgrad";
-      hipLaunchKernelGGL((lk5_wgrad_kernel<DT>), dim3(slabs), dim3(256), l5, st, a, tilesX, tilesY, (int)(ntiles / slabs), (int)(ntiles % slabs), xb, db);
-      SRK_LAUNCH_CHECK();
-      return 0;
-    }
-  }
-  static const bool no_packed = [] { const char* e = srk_dbg_getenv("SRK_NO_LK_PACKED"); return e && e[0] == '1'; }();      // A/B knob
-  if (a.cout_real > 0 && a.cout_real <= 6 && a.cout_real * K <= 32 && !no_packed) {
-    // few real output channels (SRResNet's tail: 3): MFMA columns = (kw, co) pairs
-    constexpr int plds = 2 * (16 * XWP * 128 + 16 * 16 * 32) + 8 * 16 * (16 + 2 * (K - 1) + 16) * 2 + 2 * 16 * 64 * 4;
-    static_assert(plds <= 160 * 1024, "LDS");
-    static const hipError_t pattr = hipFuncSetAttribute(reinterpret_cast<const void*>(&lk_wgrad_packed_kernel<DT, K>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (pattr != hipSuccess) { srk_set_error("srk_conv2d_wgrad: cannot reserve LDS"); return (int)pattr; }
-    srk_kernel_name = LK_NAME_K("lk_wgrad_packed<");
-    hipLaunchKernelGGL((lk_wgrad_packed_kernel<DT, K>), dim3(slabs, K), dim3(256), plds, st, a, tilesX, tilesY, (int)ntiles, (int)(ntiles / slabs), (int)(ntiles % slabs), xb, db);
-    SRK_LAUNCH_CHECK();
-    return 0;
-  }
-  srk_kernel_name = LK_NAME_K("lk_wgrad<");
-  hipLaunchKernelGGL((lk_wgrad_kernel<DT, K>), dim3(slabs, K), dim3(256), lds, st, a, tilesX, tilesY, (int)ntiles, (int)(ntiles / slabs), (int)(ntiles % slabs), xb, db);
-  SRK_LAUNCH_CHECK();
-  return 0;
-}
-template <int DT> static int lk_wgrad_launch_dt(const srk_wgrad_args& a, hipStream_t st) {
-  switch (a.KH) {
-    case 5: return lk_wgrad_launch_k<DT, 5>(a, st);
-    case 7: return lk_wgrad_launch_k<DT, 7>(a, st);
-    default: return lk_wgrad_launch_k<DT, 9>(a, st);
-  }
-}
 int srk_wgrad_lk_launch(const srk_wgrad_args& a, hipStream_t st) {
-  return a.dtype == SRK_BF16 ? lk_wgrad_launch_dt<SRK_BF16>(a, st) : lk_wgrad_launch_dt<SRK_F16>(a, st);
+  if (lk_all_rows(a)) return lk_by_dtype_k<LkAllRowsLaunch>(a, st);
+  if (lk5_wgrad_ok(a)) return lk_by_dtype<Lk5WgradLaunch>(a, st);
+  static const bool no_packed = [] { const char* e = srk_dbg_getenv("SRK_NO_LK_PACKED"); return e && e[0] == '1'; }();      // A/B knob
+  // few real output channels (SRResNet's tail: 3): MFMA columns = (kw, co) pairs
+  if (a.cout_real > 0 && a.cout_real <= LkPackedCfg<5>::MAXC && a.cout_real * a.KH <= 32 && !no_packed) return lk_by_dtype_k<LkPackedLaunch>(a, st);
+  return lk_by_dtype_k<LkWgradLaunch>(a, st);
 }

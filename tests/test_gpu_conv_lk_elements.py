@@ -67,13 +67,17 @@ PATH_KERNELS = {
     "lk_wgrad": ("lk_conv<8,1,7>", "lk_conv<2,2,7>", "lk_wgrad<7>"),
     "lk5_wgrad": ("lk_conv<8,1,5>", "lk5_dgrad", "lk5_wgrad"),
     "lk5_wgrad (the collapsed HR stage's shape)": ("lk_conv<8,1,5>", "lk5_dgrad", "lk5_wgrad"),
+    # 2 x 2 ragged 16-pixel tiles = 3 x 2 ragged 8-row tiles: a partial tile in both directions and more than one tile per direction
+    "allrows, 5x5": ("lk_conv_rows<5>", "lk5_dgrad", "lk_wgrad_allrows<5>"),
+    "lk_wgrad, 9x9": ("lk_conv<8,1,9>", "lk_conv<2,2,9>", "lk_wgrad<9>"),
 }
 
 
 @pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("k,cout,n,h,w,path", [(9, 3, 2, 40, 33, "lk_wgrad_allrows / lk_conv_rows"), (9, 1, 1, 35, 20, "allrows"), (5, 6, 1, 33, 33, "lk_wgrad_packed"),
                                                 (7, 4, 2, 16, 47, "allrows, 7x7"), (7, 16, 2, 17, 30, "lk_wgrad"), (5, 8, 1, 21, 19, "lk5_wgrad"),
-                                                (5, 12, 3, 48, 48, "lk5_wgrad (the collapsed HR stage's shape)")])
+                                                (5, 12, 3, 48, 48, "lk5_wgrad (the collapsed HR stage's shape)"), (5, 3, 1, 17, 18, "allrows, 5x5"),
+                                                (9, 16, 1, 17, 18, "lk_wgrad, 9x9")])
 def test_large_kernel_convs_per_element_on_rounded_inputs(A, dt, k, cout, n, h, w, path):
     import torch.nn.functional as F
     from sr_amd import ops
