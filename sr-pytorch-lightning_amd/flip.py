@@ -54,8 +54,8 @@ _RGB2XYZ = np.array([[10135552 / 24577794, 8788810 / 24577794, 4435075 / 2457779
 _TAB_CSF_A, _TAB_CSF_RG, _TAB_CSF_BY1, _TAB_CSF_BY2 = 0, 21, 42, 63
 _TAB_EDGE, _TAB_POINT, _TAB_GAUSS = 84, 103, 122
 _TAB_BY_W, _TAB_REDIST, _TAB_M, _TAB_MINV, _TAB_WHITE = 141, 143, 147, 156, 165
-TABLE_FLOATS = 176
-ADJ_CHANNELS = 7                # d err / d(filtered test Y, Cx, Cz), d err / d(test edge x, edge y, point x, point y)
+TABLE_FLOATS = L.SRK_FLIP_TABLE_FLOATS
+ADJ_CHANNELS = L.SRK_FLIP_ADJ_CHANNELS      # d err / d(filtered test Y, Cx, Cz), d err / d(test edge x, edge y, point x, point y)
 
 
 def _csf_radius(ppd):

@@ -510,7 +510,7 @@ class HrTailFn(torch.autograd.Function):
     def _args(x, wu, bu, wt, bt, bufs, **kw):
         n, h, w, _ = x.shape
         o, c = wt.shape[0], wt.shape[1]
-        return L.HrTailArgs(wt=wt.data_ptr(), bt=_ptr(bt), wu=wu.data_ptr(), bu=_ptr(bu), O=o, C=c, Ci=wu.shape[1],
+        return L.HrtailArgs(wt=wt.data_ptr(), bt=_ptr(bt), wu=wu.data_ptr(), bu=_ptr(bu), O=o, C=c, Ci=wu.shape[1],
                             weff=bufs["weff"].data_ptr(), beff=bufs["beff"].data_ptr(), wedge=bufs["wedge"].data_ptr(),
                             bedge=bufs["bedge"].data_ptr(), wcor=bufs["wcor"].data_ptr(), bcor=bufs["bcor"].data_ptr(),
                             x=x.data_ptr(), x_pitch=_pitch(x), N=n, H=h, W=w, dtype=_DT[x.dtype], **kw)

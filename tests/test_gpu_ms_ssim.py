@@ -11,7 +11,6 @@ pytestmark = pytest.mark.gpu
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ms_ssim_ref as R  # noqa: E402
-from test_host_surface import _header_struct_fields  # noqa: E402
 from test_ms_ssim_cpu import SHAPES, images  # noqa: E402
 
 GPU_SHAPES = SHAPES + [(1, 3, 1356, 2040), (4, 3, 192, 192)]
@@ -112,8 +111,7 @@ def test_model_metric_and_validation_epoch(A):
 
 def test_c_abi_refuses_and_mirrors_the_header(A):
     L = A._lib
-    kind = {ctypes.c_void_p: "p", ctypes.c_int: "i", ctypes.c_float: "f", ctypes.c_longlong: "q"}
-    assert [(n, kind[t]) for n, t in L.MsSsimArgs._fields_] == _header_struct_fields("srk_ms_ssim_args")
+    assert L.STRUCTS["srk_ms_ssim_args"] is L.MsSsimArgs       # its layout: tests/test_host_surface.py
     lib = L.load()
     x = torch.rand(1, 3, 200, 200, device="cuda")
     ws = torch.empty(1 << 22, dtype=torch.uint8, device="cuda")

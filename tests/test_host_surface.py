@@ -1,10 +1,14 @@
 """CPU tests of the product's host side: the C-ABI library loads and exports what include/srk.h declares,
-the ctypes structs mirror the header, the model classes keep the reference's constructor / state_dict /
-init contract, the HIP path refuses to run without a GPU, and config 0 (SRCNN x2 on CPU) works."""
+the ctypes binding derived from the header has the C compiler's struct layouts, the prototypes and the constants,
+the model classes keep the reference's constructor / state_dict / init contract, the HIP path refuses to run
+without a GPU, and config 0 (SRCNN x2 on CPU) works."""
 import ctypes
 import json
 import os
 import re
+import shutil
+import subprocess
+import types
 
 import numpy as np
 import pytest
@@ -34,42 +38,181 @@ def test_library_exports_every_declared_symbol():
     assert [lib.srk_conv_tile(c) for c in (3, 48, 64, 102, 128, 192, 256, 768)] == [32, 64, 64, 128, 128, 64, 128, 128]
 
 
-def _header_struct_fields(name):
-    header = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)          # comments first: some contain braces
-    body = re.search(r"typedef struct(?:\s+\w+)?\s*\{([^{}]*)\}\s*" + name + r"\s*;", header).group(1)
-    fields = []
-    for stmt in body.split(";"):
-        stmt = stmt.strip()
-        if not stmt:
-            continue
-        # "const void* x" / "int x_pitch, x_coff" / "float scale"
-        m = re.match(r"(const\s+)?(void|float|int|double|long long|signed char|uint8_t|unsigned int|srk_patch_desc|srk_adam_slot|srk_adam_block)\s*(\*?)\s*(.*)", stmt)
-        base, ptr, rest = m.group(2), m.group(3), m.group(4)
-        base = {"long long": "q"}.get(base, base)
-        for nm in rest.split(","):
-            nm = nm.strip()
-            is_ptr = bool(ptr) or nm.startswith("*")
-            fields.append((nm.lstrip("* "), "p" if is_ptr else base[0]))
-    return fields
+# ---- the binding derived from include/srk.h (sr_amd._lib) -----------------------------------------------------------------------------
+L = sr_amd._lib
+HEADER_CODE = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)          # comments out first: some contain braces and calls
 
 
-@pytest.mark.parametrize("cname,cls", [("srk_pack_args", "PackArgs"), ("srk_conv_args", "ConvArgs"), ("srk_wgrad_args", "WgradArgs"),
-                                        ("srk_wgrad_fin_args", "WgradFinArgs"), ("srk_unfold_args", "UnfoldArgs"),
-                                        ("srk_to_nhwc_args", "ToNhwcArgs"), ("srk_to_nchw_args", "ToNchwArgs"),
-                                        ("srk_ca_pool_args", "CaPoolArgs"), ("srk_ca_apply_args", "CaApplyArgs"),
-                                        ("srk_ca_bwd_args", "CaBwdArgs"), ("srk_patch_desc", "PatchDesc"), ("srk_patch_args", "PatchArgs"),
-                                        ("srk_sse_args", "SseArgs"), ("srk_ssim_args", "SsimArgs"), ("srk_l1_args", "L1Args"),
-                                        ("srk_unfold_nhwc_args", "UnfoldNhwcArgs"), ("srk_fold_nhwc_args", "FoldNhwcArgs"),
-                                        ("srk_chan_stats_args", "ChanStatsArgs"), ("srk_chan_apply_args", "ChanApplyArgs"),
-                                        ("srk_conv_pair_args", "ConvPairArgs"), ("srk_adam_slot", "AdamSlot"),
-                                        ("srk_adam_block", "AdamBlock"), ("srk_adam_args", "AdamArgs"), ("srk_rowsum_job", "RowsumJob"),
-                                        ("srk_chan_finalize_args", "ChanFinalizeArgs"), ("srk_hrtail_args", "HrTailArgs")])
-def test_ctypes_structs_mirror_header(cname, cls):
-    want = _header_struct_fields(cname)
-    st = getattr(sr_amd._lib, cls)
-    kind = {ctypes.c_void_p: "p", ctypes.c_int: "i", ctypes.c_float: "f", ctypes.c_longlong: "q"}
-    got = [(n, kind[t]) for n, t in st._fields_]
-    assert got == want
+@pytest.fixture(scope="module")
+def c_layout(tmp_path_factory):
+    """What the C compiler lays out for every struct of the header: {C name: (sizeof, [offsetof of each field], [sizeof of each field])},
+    printed by one generated program that includes srk.h."""
+    cc = os.environ.get("CC") or shutil.which("cc") or os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "clang")
+    if not (shutil.which(cc) or os.path.exists(cc)):
+        pytest.fail(f"no C compiler to check the struct layouts with ($CC, cc, {cc})")
+    d = tmp_path_factory.mktemp("layout")
+    lines = ["#include <stddef.h>", "#include <stdio.h>", '#include "srk.h"', "int main(void) {"]
+    for cname, cls in L.STRUCTS.items():
+        names = [n for n, _ in cls._fields_]
+        lines.append('  printf("%s offsets %%zu%s\\n", sizeof(%s)%s);' % (
+            cname, " %zu" * len(names), cname, "".join(", offsetof(%s, %s)" % (cname, n) for n in names)))
+        lines.append('  printf("%s sizes%s\\n"%s);' % (
+            cname, " %zu" * len(names), "".join(", sizeof(((%s*)0)->%s)" % (cname, n) for n in names)))
+    (d / "layout.c").write_text("\n".join(lines + ["  return 0;", "}", ""]))
+    subprocess.run([cc, "-I", os.path.join(ROOT, "include"), "-o", str(d / "layout"), str(d / "layout.c")], check=True)
+    out = {}
+    for line in subprocess.run([str(d / "layout")], check=True, capture_output=True, text=True).stdout.splitlines():
+        cname, what, *nums = line.split()
+        out.setdefault(cname, {})[what] = [int(v) for v in nums]
+    return {c: (v["offsets"][0], v["offsets"][1:], v["sizes"]) for c, v in out.items()}
+
+
+@pytest.mark.parametrize("cname,cls", [(c, k.__name__) for c, k in L.STRUCTS.items()])
+def test_ctypes_structs_mirror_header(c_layout, cname, cls):
+    """Every struct of the binding against the C compiler's layout of include/srk.h: size, each field's offset, and each field's size
+    (a float taken for an int sits at the same offset)."""
+    st = getattr(L, cls)
+    assert st is L.STRUCTS[cname]
+    size, offsets, sizes = c_layout[cname]
+    assert ctypes.sizeof(st) == size
+    assert [getattr(st, n).offset for n, _ in st._fields_] == offsets
+    assert [getattr(st, n).size for n, _ in st._fields_] == sizes
+
+
+def test_every_struct_of_the_header_is_bound(c_layout):
+    assert len(L.STRUCTS) == len(re.findall(r"\btypedef struct\b", HEADER_CODE)) == len(c_layout) > 0
+    assert all(getattr(L, cls.__name__) is cls for cls in L.STRUCTS.values())
+
+
+# feature -> (argument struct, launchers that take it, helpers that must be bound as plain functions)
+ABI = {
+    "gmsd": ("GmsdArgs", ["srk_gmsd_fwd", "srk_gmsd_finalize", "srk_gmsd_bwd"], ["srk_gmsd_tiles"]),
+    "ssim_loss": ("SsimLossArgs", ["srk_ssim_loss_fwd", "srk_ssim_loss_finalize", "srk_ssim_loss_bwd"], ["srk_ssim_loss_tiles"]),
+    "ms_ssim_loss": ("MsSsimLossArgs", ["srk_ms_ssim_loss_fwd", "srk_ms_ssim_loss_finalize", "srk_ms_ssim_loss_bwd"],
+                     ["srk_ms_ssim_loss_workspace_bytes", "srk_ms_ssim_loss_tiles"]),
+    "ms_ssim": ("MsSsimArgs", ["srk_ms_ssim"], ["srk_ms_ssim_workspace_bytes", "srk_ms_ssim_tiles"]),
+    "haarpsi": ("HaarpsiArgs", ["srk_haarpsi_fwd", "srk_haarpsi_finalize", "srk_haarpsi_bwd"], ["srk_haarpsi_tiles"]),
+    "flip": ("FlipArgs", ["srk_flip_fwd", "srk_flip_bwd"], ["srk_flip_blocks", "srk_flip_mean"]),
+    "l1": ("L1Args", ["srk_l1_loss_fwd", "srk_l1_loss_bwd"], ["srk_l1_blocks", "srk_l1_loss_mean"]),
+    "adam": ("AdamArgs", ["srk_adam_step"], ["srk_adam_step_scaled", "srk_adam_check_scaled", "srk_adam_update_scaled"]),
+    "ranger": ("RangerArgs", ["srk_ranger_step"], ["srk_ranger_step_scaled", "srk_ranger_check_scaled", "srk_ranger_update_scaled"]),
+    "sgd": ("SgdArgs", ["srk_sgd_step"], ["srk_sgd_step_scaled", "srk_sgd_check_scaled", "srk_sgd_update_scaled"]),
+    "rmsprop": ("RmspropArgs", ["srk_rmsprop_step"], ["srk_rmsprop_step_scaled", "srk_rmsprop_check_scaled", "srk_rmsprop_update_scaled"]),
+    "ema": ("EmaArgs", ["srk_ema_step"], []),
+    "tile": ("TileArgs", ["srk_tile_gather", "srk_tile_place"], []),
+    "hrtail": ("HrtailArgs", ["srk_hrtail_collapse", "srk_hrtail_edge_fwd", "srk_hrtail_edge_bwd_x", "srk_hrtail_edge_bwd_w",
+                              "srk_hrtail_expand"], ["srk_hrtail_scratch_floats"]),
+}
+
+
+@pytest.mark.parametrize("feature", sorted(ABI))
+def test_feature_entry_points_are_bound(feature):
+    cls, launchers, helpers = ABI[feature]
+    for name in launchers:
+        assert L.LAUNCHERS[name] is getattr(L, cls), name
+        assert L.PROTOTYPES[name] == (ctypes.c_int, [ctypes.POINTER(getattr(L, cls)), ctypes.c_void_p]), name
+    for name in helpers:
+        assert name in L.OTHER_SYMBOLS and name not in L.LAUNCHERS, name
+
+
+def test_every_declared_function_has_a_prototype():
+    names = set(L.LAUNCHERS) | set(L.OTHER_SYMBOLS)
+    assert len(names) == len(L.LAUNCHERS) + len(L.OTHER_SYMBOLS) == len(re.findall(r"\bsrk_\w+\s*\(", HEADER_CODE)) > 0
+    assert names == set(L.PROTOTYPES) == set(_declared_functions())
+
+
+def test_irregular_prototypes():
+    """Pinned by hand: the prototypes that are not `int f(const srk_x_args* a, srk_stream_t stream)`."""
+    P, i, p, q = ctypes.POINTER, ctypes.c_int, ctypes.c_void_p, ctypes.c_longlong
+    want = {
+        "srk_wgrad_group_plan": (i, [P(L.WgradArgs), i, p, p, p, p, p]),
+        "srk_pw_pack_bytes": (q, [i, i, i, i]),
+        "srk_proj_pack_bytes": (q, []),
+        "srk_last_error": (ctypes.c_char_p, []),
+        "srk_pack_group_tiles": (i, [p, i, p]),                      # `host_table`: an address, not a struct instance
+        "srk_pack_conv_weights_group": (i, [p, i, p]),               # `table`
+        "srk_weight_norm_group": (i, [p, i, i, i, p]),               # `table_dev`
+        "srk_chan_stats_finalize": (i, [P(L.ChanStatsArgs), P(L.ChanFinalizeArgs), p, p]),
+        "srk_conv_trunk": (i, [P(L.ConvArgs), p, i, p]),
+        "srk_conv_bits_ok": (i, [P(L.ConvArgs)]),
+        "srk_l1_blocks": (i, [q]),
+        "srk_upload_small": (i, [p, p, q, p]),
+    }
+    for name, proto in want.items():
+        assert L.PROTOTYPES[name] == proto, name
+        assert name in L.OTHER_SYMBOLS
+
+
+def _stub_library(without=()):
+    return types.SimpleNamespace(**{n: types.SimpleNamespace() for n in L.PROTOTYPES if n not in without})
+
+
+def test_bind_sets_every_prototype_on_any_object():
+    lib = L.bind(_stub_library(), False)
+    for name, (restype, argtypes) in L.PROTOTYPES.items():
+        fn = getattr(lib, name)
+        assert fn.restype is restype and fn.argtypes == argtypes, name
+
+
+def test_bind_of_a_library_that_lacks_a_symbol():
+    with pytest.raises(RuntimeError, match="srk_gmsd_tiles"):
+        L.bind(_stub_library(without=["srk_gmsd_tiles"]), False)
+    lib = L.bind(_stub_library(without=["srk_gmsd_tiles"]), True)            # an older build, loaded through SRK_LIB_PATH
+    assert lib.srk_gmsd_fwd.restype is ctypes.c_int
+    with pytest.raises(RuntimeError, match="srk_gmsd_tiles is not exported by .*SRK_LIB_PATH"):
+        lib.srk_gmsd_tiles(1, 3, 8, 8)
+
+
+def test_parser_on_a_small_header():
+    h = L.parse_header("""
+        /* a comment with { braces } and srk_call( */
+        #define SRK_N 12
+        enum { SRK_A = 0, SRK_B = -3 };
+        typedef void* srk_stream_t;
+        typedef struct srk_two_part_args { const float *a, *b; int n, m; long long P; double lr; unsigned int* t; } srk_two_part_args;
+        int srk_go(const srk_two_part_args* a, srk_stream_t stream);
+        int srk_go_group(const srk_two_part_args* table_dev, int n, srk_stream_t stream);
+        long long srk_bytes(void);
+        const char* srk_name(const srk_two_part_args* a,
+                             float* out);
+    """)
+    p, cls = ctypes.c_void_p, h.structs["srk_two_part_args"]
+    assert cls.__name__ == "TwoPartArgs" and issubclass(cls, ctypes.Structure)
+    assert cls._fields_ == [("a", p), ("b", p), ("n", ctypes.c_int), ("m", ctypes.c_int), ("P", ctypes.c_longlong),
+                            ("lr", ctypes.c_double), ("t", p)]
+    assert h.consts == {"SRK_N": 12, "SRK_A": 0, "SRK_B": -3}
+    assert h.launchers == {"srk_go": cls}
+    assert h.protos == {"srk_go": (ctypes.c_int, [ctypes.POINTER(cls), p]), "srk_go_group": (ctypes.c_int, [p, ctypes.c_int, p]),
+                        "srk_bytes": (ctypes.c_longlong, []), "srk_name": (ctypes.c_char_p, [ctypes.POINTER(cls), p])}
+
+
+@pytest.mark.parametrize("text,quoted", [
+    ("typedef struct { const float* x; short n; } srk_bad_args;", "short n"),                        # an unknown field type
+    ("typedef struct { int a; struct { int b; } inner; } srk_bad_args;", "struct { int b"),          # a nested struct
+    ("typedef struct { int a; float w[5]; } srk_bad_args;", "float w[5]"),                           # an array field
+    ("typedef struct { int a; float** w; } srk_bad_args;", "float** w"),
+    ("typedef struct { int a; } srk_ok_args; typedef struct { srk_ok_args inner; } srk_bad_args;", "srk_ok_args inner"),
+    ("typedef struct { int a } srk_bad_args;", "int a"),
+    ("void srk_f(int n);", "void srk_f(int n)"),                                                     # an unknown return type
+    ("int srk_f(const srk_later_args* a, srk_stream_t stream);", "srk_later_args* a"),               # a struct not declared yet
+    ("int srk_f(unsigned n);", "unsigned n"),
+    ("enum { SRK_A = 0, SRK_B };", "SRK_B"),
+    ("#define SRK_F(x) (x)", "#define SRK_F(x) (x)"),
+    ("#pragma pack(1)", "#pragma pack(1)"),
+    ("int srk_f(int n)", "int srk_f(int n)"),                                                        # no `;`
+])
+def test_parser_refuses_and_quotes_what_it_does_not_understand(text, quoted):
+    with pytest.raises(ValueError, match=re.escape(quoted)):
+        L.parse_header(text)
+
+
+def test_constants_come_from_the_header():
+    assert (L.SRK_BF16, L.SRK_F16, L.SRK_F32) == (0, 1, 2)
+    assert (L.OUT_NHWC, L.OUT_NHWC_PS, L.OUT_PLANAR) == (L.SRK_OUT_NHWC, L.SRK_OUT_NHWC_PS, L.SRK_OUT_PLANAR) == (0, 1, 2)
+    assert (L.EMA_UPDATE, L.EMA_SWAP, L.EMA_STORE, L.EMA_LOAD) == (L.SRK_EMA_UPDATE, L.SRK_EMA_SWAP, L.SRK_EMA_STORE, L.SRK_EMA_LOAD) == (0, 1, 2, 3)
+    assert (L.SRK_E_BADARG, L.SRK_E_NODEV) == (-1, -2)
+    assert sr_amd.flip.TABLE_FLOATS == L.SRK_FLIP_TABLE_FLOATS == 176
+    assert sr_amd.flip.ADJ_CHANNELS == L.SRK_FLIP_ADJ_CHANNELS == 7
 
 
 @pytest.mark.parametrize("name", sorted(MANIFEST))

@@ -4,7 +4,6 @@ rest on), the zero-gradient rule of a plane whose value is 0, the clamp, the los
 the ctypes mirror of the header, the library's host-side geometry and train.py."""
 import ctypes
 import os
-import re
 import subprocess
 import sys
 
@@ -223,15 +222,7 @@ def test_mismatched_shapes_raise(ML):
 # ---- the C ABI -------------------------------------------------------------------------------------------------------------------
 def test_ms_ssim_loss_args_mirror_the_header():
     import sr_amd
-    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "srk.h")).read(), flags=re.S)
-    body = re.search(r"typedef struct\s+srk_ms_ssim_loss_args\s*\{([^{}]*)\}\s*srk_ms_ssim_loss_args\s*;", header).group(1)
-    want = []
-    for stmt in filter(None, (x.strip() for x in body.split(";"))):
-        m = re.match(r"(const\s+)?(float|double|int)\s*(\*?)\s*(.*)", stmt)
-        for nm in m.group(4).split(","):
-            want.append((nm.strip(), "p" if m.group(3) else m.group(2)[0]))
-    kind = {ctypes.c_void_p: "p", ctypes.c_int: "i", ctypes.c_float: "f", ctypes.c_double: "d"}
-    assert [(n, kind[t]) for n, t in sr_amd._lib.MsSsimLossArgs._fields_] == want
+    assert sr_amd._lib.STRUCTS["srk_ms_ssim_loss_args"] is sr_amd._lib.MsSsimLossArgs       # its layout: tests/test_host_surface.py
     names = ["srk_ms_ssim_loss_" + k for k in ("fwd", "finalize", "bwd")]
     assert set(names) <= set(sr_amd._lib.LAUNCHERS)
     assert all(sr_amd._lib.LAUNCHERS[n] is sr_amd._lib.MsSsimLossArgs for n in names)

@@ -3,15 +3,12 @@ against the header, the model's optimizer table, CPU parameters stepping through
 that go to torch.optim and back, and what the constructors reject."""
 import copy
 import ctypes
-import os
-import re
 
 import pytest
 import torch
 
 import sr_amd
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 SHAPES = [(1,), (3,), (7, 5, 3, 3), (4097,), (33, 10)]
 SGD_HYPER = [dict(), dict(lr=3e-2, momentum=0.9), dict(lr=3e-2, momentum=0.9, dampening=0.1, weight_decay=1e-2),
@@ -42,18 +39,10 @@ def _set(ps, gs):
 
 @pytest.mark.parametrize("name", ["sgd", "rmsprop"])
 def test_args_mirror_the_header(name):
-    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "srk.h")).read(), flags=re.S)
-    body = re.search(r"typedef struct\s*\{([^{}]*)\}\s*srk_%s_args\s*;" % name, header).group(1)
-    want = []
-    for stmt in filter(None, (x.strip() for x in body.split(";"))):
-        m = re.match(r"(const\s+)?(srk_adam_slot|srk_adam_block|float|double|int)\s*(\*?)\s*(.*)", stmt)
-        for nm in m.group(4).split(","):
-            want.append((nm.strip(), "p" if m.group(3) else m.group(2)[0]))
-    kind = {ctypes.c_void_p: "p", ctypes.c_int: "i", ctypes.c_float: "f", ctypes.c_double: "d"}
     st = {"sgd": sr_amd._lib.SgdArgs, "rmsprop": sr_amd._lib.RmspropArgs}[name]
-    assert [(n, kind[t]) for n, t in st._fields_] == want
+    assert sr_amd._lib.STRUCTS["srk_%s_args" % name] is st       # its layout: tests/test_host_surface.py
     for sfx in ("_step", "_step_scaled", "_check_scaled", "_update_scaled"):
-        assert re.search(r"\bint srk_%s%s\(" % (name, sfx), header), sfx
+        assert sr_amd._lib.PROTOTYPES["srk_%s%s" % (name, sfx)][0] is ctypes.c_int, sfx
         assert ("srk_%s%s" % (name, sfx)) in set(sr_amd._lib.LAUNCHERS) | set(sr_amd._lib.OTHER_SYMBOLS)
 
 

@@ -14,7 +14,6 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import tiling_ref as TR  # noqa: E402
 from oracle import functional as OF  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EPS64 = 2.0 ** -52
 
 
@@ -254,19 +253,8 @@ def test_predict_cli_tiled_self_ensemble_on_cpu(tmp_path):
 
 
 def test_header_and_binding_agree_on_the_tile_structs():
-    """The two structs of csrc/tile.hip, field for field (tests/test_host_surface.py checks its own list of structs, and that the
-    entry points are declared, bound and exported)."""
-    import ctypes
-    import re
+    """The two structs of csrc/tile.hip are the header's (tests/test_host_surface.py checks every struct's layout against the C
+    compiler's, and that the entry points are declared, bound and exported)."""
     import sr_amd as A
-    header = open(os.path.join(ROOT, "include", "srk.h")).read()
-    header = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
-    kind = {ctypes.c_void_p: "p", ctypes.c_int: "i", ctypes.c_float: "f"}
-    for cname, cls in (("srk_tile_desc", A._lib.TileDesc), ("srk_tile_args", A._lib.TileArgs)):
-        body = re.search(r"typedef struct\s*\{([^{}]*)\}\s*" + cname + r"\s*;", header).group(1)
-        want = []
-        for stmt in filter(None, (s.strip() for s in body.split(";"))):
-            m = re.match(r"(const\s+)?(\w+)\s*(\*?)\s*(.*)", stmt)
-            for nm in m.group(4).split(","):
-                want.append((nm.strip().lstrip("* "), "p" if (m.group(3) or nm.strip().startswith("*")) else m.group(2)[0]))
-        assert [(n, kind[t]) for n, t in cls._fields_] == want
+    assert A._lib.STRUCTS["srk_tile_desc"] is A._lib.TileDesc and A._lib.STRUCTS["srk_tile_args"] is A._lib.TileArgs
+    assert A._lib.LAUNCHERS["srk_tile_gather"] is A._lib.LAUNCHERS["srk_tile_place"] is A._lib.TileArgs
