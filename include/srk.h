@@ -881,7 +881,11 @@ int srk_hrtail_expand(const srk_hrtail_args* a, srk_stream_t stream);
  *     p -= lr / (1 - beta1^t) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
  * `steps` (device floats: the number of updates each tensor has had -- torch counts per parameter, a tensor without a
  * gradient skips the step) are advanced by the call itself (a second tiny launch) for the tensors in the table, so a
- * captured hipGraph can replay it; `ticket` is reserved (may be NULL).                                                   */
+ * captured hipGraph can replay it; `ticket` is reserved (may be NULL).
+ * `lr_dev` (this struct and the three optimizers' below): NULL, or the address of ONE DEVICE double that every entry point of the
+ * family reads when the launch RUNS -- a replayed hipGraph follows a learning rate that srk_lr_sched_step (or an upload) wrote
+ * between two replays.  The value is rounded exactly where the by-value `lr` is: (float)lr here, (float)(-s*lr), (float)(-wd*lr),
+ * (float)(-lr) below.  With `lr_dev` the by-value `lr` is neither read nor range-checked.                                  */
 typedef struct { float* p; const float* g; long long state_off; long long n; long long step_idx; } srk_adam_slot;
 typedef struct { int slot; int count; long long start; } srk_adam_block;
 typedef struct {
@@ -890,6 +894,7 @@ typedef struct {
   float* steps; unsigned int* ticket;
   float lr, beta1, beta2, eps, weight_decay; int maximize;
   float one_minus_beta1, one_minus_beta2;   /* 1 - beta rounded from double, as torch forms them */
+  const double* lr_dev;                     /* NULL: `lr` above.  Else ONE DEVICE double read when the launch RUNS (srk_lr_sched_step) */
 } srk_adam_args;
 int srk_adam_step(const srk_adam_args* a, srk_stream_t stream);
 /* The same update under DYNAMIC LOSS SCALING kept on the device (fp16 training: the reference's `precision: 16` runs Lightning's
@@ -925,6 +930,7 @@ typedef struct {
   float* steps;
   double lr, beta1, beta2, alpha, n_sma_threshold, eps, weight_decay;
   int k;
+  const double* lr_dev;                     /* NULL: `lr` above; else as srk_adam_args.lr_dev */
 } srk_ranger_args;
 int srk_ranger_step(const srk_ranger_args* a, srk_stream_t stream);
 int srk_ranger_step_scaled(const srk_ranger_args* a, float* scaler_state, srk_stream_t stream);
@@ -952,6 +958,7 @@ typedef struct {
   float* steps;
   double lr, momentum, dampening, weight_decay;
   int nesterov, maximize;
+  const double* lr_dev;                     /* NULL: `lr` above; else as srk_adam_args.lr_dev */
 } srk_sgd_args;
 int srk_sgd_step(const srk_sgd_args* a, srk_stream_t stream);
 int srk_sgd_step_scaled(const srk_sgd_args* a, float* scaler_state, srk_stream_t stream);
@@ -973,6 +980,7 @@ typedef struct {
   float* steps;
   double lr, alpha, eps, weight_decay, momentum;
   int centered, maximize;
+  const double* lr_dev;                     /* NULL: `lr` above; else as srk_adam_args.lr_dev */
 } srk_rmsprop_args;
 int srk_rmsprop_step(const srk_rmsprop_args* a, srk_stream_t stream);
 int srk_rmsprop_step_scaled(const srk_rmsprop_args* a, float* scaler_state, srk_stream_t stream);
@@ -999,6 +1007,41 @@ typedef struct {
   int op;
 } srk_ema_args;
 int srk_ema_step(const srk_ema_args* a, srk_stream_t stream);
+
+/* ---- learning-rate schedules on the device (lr_sched.py), csrc/lr_sched.hip ------------------------------------------------------
+ * One tiny launch that keeps a schedule's step count and the learning rate of every parameter group in DEVICE memory, where the
+ * optimizers' `lr_dev` reads them: a captured step that ends in SRK_LR_ADVANCE follows the schedule replay after replay.
+ *   count   : ONE device 64-bit integer, the number of optimizer steps so far (t)
+ *   lr      : device double [ngroups], written:  lr[g] = f(t, base_lr[g])
+ *   base_lr : device double [ngroups], read
+ *   op      : SRK_LR_SET      count = value;  lr = f(count)        (creation, load_state_dict)
+ *             SRK_LR_ADVANCE  count += 1;     lr = f(count)        (behind every optimizer step)
+ * f(t, base) = warm(t) * main(t, base), in DOUBLE, torch.optim.lr_scheduler's closed forms:
+ *   warm  : 1 if warmup_steps == 0, else warmup_start + (1 - warmup_start) * min(t, W) / W          LinearLR(warmup_start, 1, W)
+ *   SRK_LR_CONSTANT        : base
+ *   SRK_LR_STEP            : base * gamma^(t / step_size)  (integer division)                        StepLR
+ *   SRK_LR_MULTISTEP       : base * gamma^(number of milestones <= t)                                MultiStepLR
+ *   SRK_LR_COSINE          : eta_min + (base - eta_min) * (1 + cos(pi * t / t_max)) / 2              CosineAnnealingLR (periodic past t_max)
+ *   SRK_LR_COSINE_RESTARTS : the same in T_cur / T_i, found by the integer loop
+ *                            T_cur = t, T_i = t_0;  while (T_cur >= T_i) { T_cur -= T_i; T_i *= t_mult; }   CosineAnnealingWarmRestarts
+ * Only the constants of `kind` (and the warm-up's) are read and checked: step_size >= 1, t_max >= 1, t_0 >= 1, t_mult >= 1, at most
+ * SRK_LR_MAX_MILESTONES milestones m0 <= m1 <= ... (the first `nmilestones` of m0..m15); always: 0 < warmup_start <= 1 (1 without a
+ * warm-up), warmup_steps >= 0, value >= 0 for SRK_LR_SET.  One workgroup, one thread per group, ordinary stores. */
+enum { SRK_LR_CONSTANT = 0, SRK_LR_STEP = 1, SRK_LR_MULTISTEP = 2, SRK_LR_COSINE = 3, SRK_LR_COSINE_RESTARTS = 4 };
+enum { SRK_LR_SET = 0, SRK_LR_ADVANCE = 1 };
+#define SRK_LR_MAX_MILESTONES 16
+typedef struct {
+  long long* count; double* lr; const double* base_lr; int ngroups;
+  int kind, op;
+  long long value;
+  long long step_size; double gamma;
+  int nmilestones;
+  long long m0, m1, m2, m3, m4, m5, m6, m7, m8, m9, m10, m11, m12, m13, m14, m15;
+  long long t_max; double eta_min;
+  long long t_0, t_mult;
+  long long warmup_steps; double warmup_start;
+} srk_lr_sched_args;
+int srk_lr_sched_step(const srk_lr_sched_args* a, srk_stream_t stream);
 
 /* ---- tiled and self-ensemble inference (tiling.py), csrc/tile.hip -------------------------------------------------------------
  * The two data movements around the model's forward when a large image is predicted as a batch of overlapping tiles and / or as the

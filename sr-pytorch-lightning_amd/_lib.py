@@ -142,6 +142,7 @@ globals().update(_H.consts)             # SRK_BF16, SRK_E_BADARG, SRK_FLIP_TABLE
 globals().update({cls.__name__: cls for cls in STRUCTS.values()})       # ConvArgs, WgradArgs, ...
 OUT_NHWC, OUT_NHWC_PS, OUT_PLANAR = SRK_OUT_NHWC, SRK_OUT_NHWC_PS, SRK_OUT_PLANAR                    # noqa: F821
 EMA_UPDATE, EMA_SWAP, EMA_STORE, EMA_LOAD = SRK_EMA_UPDATE, SRK_EMA_SWAP, SRK_EMA_STORE, SRK_EMA_LOAD   # noqa: F821
+LR_SET, LR_ADVANCE = SRK_LR_SET, SRK_LR_ADVANCE                                                       # noqa: F821  (lr_sched.py: LrSchedArgs)
 
 _lib = None
 

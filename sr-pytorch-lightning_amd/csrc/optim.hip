@@ -53,7 +53,8 @@ __global__ __launch_bounds__(TABLE_NT) void adam_group_kernel(const srk_adam_arg
   const srk_adam_slot& sl = r.sl;
   const float t = a.steps[sl.step_idx] + 1.f;
   const float bc1 = 1.f - powf(a.beta1, t), bc2 = 1.f - powf(a.beta2, t);
-  const float step_size = a.lr / bc1, bc2s = sqrtf(bc2);
+  const float lr = a.lr_dev ? (float)a.lr_dev[0] : a.lr;    // block-uniform: one scalar load when the launch runs (srk.h `lr_dev`)
+  const float step_size = lr / bc1, bc2s = sqrtf(bc2);
   const float b2 = a.beta2, eps = a.eps, wd = a.weight_decay, omb1 = a.one_minus_beta1, omb2 = a.one_minus_beta2;
   auto upd = [&](float (&x)[3], float gv) {
     float &pv = x[0], &mv = x[1], &vv = x[2];
@@ -101,8 +102,9 @@ __global__ __launch_bounds__(TABLE_NT, SCALED ? 3 : 4) void ranger_group_kernel(
   b.rect = n_sma > a.n_sma_threshold;
   const double s = b.rect ? sqrt((1.0 - b2t) * (n_sma - 4.0) / (n_max - 4.0) * (n_sma - 2.0) / n_sma * n_max / (n_max - 2.0)) / (1.0 - pow(a.beta1, td))
                           : 1.0 / (1.0 - pow(a.beta1, td));
-  b.step = (float)(-s * a.lr);
-  b.decay = (float)(-a.weight_decay * a.lr);
+  const double lr = a.lr_dev ? a.lr_dev[0] : a.lr;          // block-uniform: one scalar load when the launch runs (srk.h `lr_dev`)
+  b.step = (float)(-s * lr);
+  b.decay = (float)(-a.weight_decay * lr);
   b.b1 = (float)a.beta1; b.b2 = (float)a.beta2;
   b.omb1 = (float)(1.0 - a.beta1); b.omb2 = (float)(1.0 - a.beta2);
   b.eps = (float)a.eps; b.alpha = (float)a.alpha;
@@ -153,7 +155,7 @@ __global__ __launch_bounds__(TABLE_NT, 7) void sgd_group_kernel(const srk_sgd_ar
   const TableRange r = table_range(a.slots, a.blocks);
   const srk_adam_slot& sl = r.sl;
   const float mom = (float)a.momentum, omd = (float)(1.0 - a.dampening);
-  const float wd = (float)a.weight_decay, nlr = (float)(-a.lr);
+  const float wd = (float)a.weight_decay, nlr = (float)(-(a.lr_dev ? a.lr_dev[0] : a.lr));   // (srk.h `lr_dev`: a scalar load)
   const bool has_wd = a.weight_decay != 0.0, nesterov = a.nesterov != 0, maximize = a.maximize != 0;
   bool first = false;
   if constexpr (MOM) first = a.steps[sl.step_idx] == 0.f;
@@ -193,7 +195,7 @@ __global__ __launch_bounds__(TABLE_NT) void rmsprop_group_kernel(const srk_rmspr
   const srk_adam_slot& sl = r.sl;
   const float alpha = (float)a.alpha, oma = (float)(1.0 - a.alpha), eps = (float)a.eps;
   const float mom = (float)a.momentum;
-  const float wd = (float)a.weight_decay, nlr = (float)(-a.lr);
+  const float wd = (float)a.weight_decay, nlr = (float)(-(a.lr_dev ? a.lr_dev[0] : a.lr));   // (srk.h `lr_dev`: a scalar load)
   const bool has_wd = a.weight_decay != 0.0, maximize = a.maximize != 0;
   const bool lerp_low = oma < 0.5f;          // at::lerp's two forms
   const float omw = 1.f - oma;
@@ -233,7 +235,7 @@ __global__ __launch_bounds__(TABLE_NT) void rmsprop_group_kernel(const srk_rmspr
 }
 
 // ---- launches -------------------------------------------------------------------------------------------------------------------
-// <name>_check_args refuses bad arguments in the name of the entry point `fn`; <name>_launch is the update and, where the optimizer
+// <name>_check_args refuses bad arguments in the name of the entry point `fn` (the by-value `lr` only when no `lr_dev` replaces it); <name>_launch is the update and, where the optimizer
 // keeps counts, the bump (`scaler_state` NULL: no loss scaling).
 template <class ARGS>
 void check_launch(const ARGS* a, float* scaler_state, hipStream_t st) {
@@ -249,7 +251,7 @@ void bump_launch(const ARGS* a, const float* scaler_state, hipStream_t st) {
 int adam_check_args(const srk_adam_args* a, const char* fn) {
   SRK_CHECK_ARG(a && a->slots && a->blocks && a->m && a->v && a->steps, "%s: null pointer", fn);
   SRK_CHECK_ARG(a->nblocks > 0 && a->nslots > 0, "%s: %d blocks, %d tensors", fn, a->nblocks, a->nslots);
-  SRK_CHECK_ARG(a->beta1 >= 0.f && a->beta1 < 1.f && a->beta2 >= 0.f && a->beta2 < 1.f && a->eps >= 0.f && a->lr >= 0.f,
+  SRK_CHECK_ARG(a->beta1 >= 0.f && a->beta1 < 1.f && a->beta2 >= 0.f && a->beta2 < 1.f && a->eps >= 0.f && (a->lr_dev || a->lr >= 0.f),
                 "%s: lr=%g betas=(%g, %g) eps=%g", fn, a->lr, a->beta1, a->beta2, a->eps);
   return 0;
 }
@@ -264,7 +266,7 @@ void adam_launch(const srk_adam_args* a, const float* scaler_state, hipStream_t 
 int ranger_check_args(const srk_ranger_args* a, const char* fn) {
   SRK_CHECK_ARG(a && a->slots && a->blocks && a->m && a->v && a->slow && a->steps, "%s: null pointer", fn);
   SRK_CHECK_ARG(a->nblocks > 0 && a->nslots > 0, "%s: %d blocks, %d tensors", fn, a->nblocks, a->nslots);
-  SRK_CHECK_ARG(a->lr > 0.0 && a->alpha >= 0.0 && a->alpha <= 1.0 && a->k >= 1 && a->beta1 >= 0.0 && a->beta1 < 1.0 &&
+  SRK_CHECK_ARG((a->lr_dev || a->lr > 0.0) && a->alpha >= 0.0 && a->alpha <= 1.0 && a->k >= 1 && a->beta1 >= 0.0 && a->beta1 < 1.0 &&
                 a->beta2 >= 0.0 && a->beta2 < 1.0 && a->eps >= 0.0 && a->weight_decay >= 0.0,
                 "%s: lr=%g alpha=%g k=%d betas=(%g, %g) eps=%g weight_decay=%g", fn, a->lr, a->alpha, a->k, a->beta1, a->beta2,
                 a->eps, a->weight_decay);
@@ -282,7 +284,7 @@ int sgd_check_args(const srk_sgd_args* a, const char* fn) {
   SRK_CHECK_ARG(a && a->slots && a->blocks, "%s: null table", fn);
   SRK_CHECK_ARG(a->nblocks > 0 && a->nslots > 0, "%s: %d blocks, %d tensors", fn, a->nblocks, a->nslots);
   SRK_CHECK_ARG(a->momentum == 0.0 || (a->buf && a->steps), "%s: momentum=%g needs the momentum buffer and the counts", fn, a->momentum);
-  SRK_CHECK_ARG(a->lr >= 0.0 && a->momentum >= 0.0 && a->weight_decay >= 0.0 && (!a->nesterov || (a->momentum > 0.0 && a->dampening == 0.0)),
+  SRK_CHECK_ARG((a->lr_dev || a->lr >= 0.0) && a->momentum >= 0.0 && a->weight_decay >= 0.0 && (!a->nesterov || (a->momentum > 0.0 && a->dampening == 0.0)),
                 "%s: lr=%g momentum=%g dampening=%g weight_decay=%g nesterov=%d", fn, a->lr, a->momentum, a->dampening, a->weight_decay, a->nesterov);
   return 0;
 }
@@ -305,7 +307,7 @@ int rmsprop_check_args(const srk_rmsprop_args* a, const char* fn) {
   SRK_CHECK_ARG(a && a->slots && a->blocks, "%s: null table", fn);
   SRK_CHECK_ARG(a->nblocks > 0 && a->nslots > 0, "%s: %d blocks, %d tensors", fn, a->nblocks, a->nslots);
   SRK_CHECK_ARG(a->sq && a->steps && (a->momentum <= 0.0 || a->buf) && (!a->centered || a->ga), "%s: null state pointer", fn);
-  SRK_CHECK_ARG(a->lr >= 0.0 && a->alpha >= 0.0 && a->eps >= 0.0 && a->momentum >= 0.0 && a->weight_decay >= 0.0,
+  SRK_CHECK_ARG((a->lr_dev || a->lr >= 0.0) && a->alpha >= 0.0 && a->eps >= 0.0 && a->momentum >= 0.0 && a->weight_decay >= 0.0,
                 "%s: lr=%g alpha=%g eps=%g momentum=%g weight_decay=%g", fn, a->lr, a->alpha, a->eps, a->momentum, a->weight_decay);
   return 0;
 }

@@ -21,6 +21,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import ema as _ema
+from .. import lr_sched as _lr_sched
 from .. import optim as _hip_optim
 from .. import tiling as _tiling
 
@@ -270,6 +271,8 @@ class SRModel(_Base):
                  tile_batch: int = _tiling.DEFAULT_TILE_BATCH,
                  self_ensemble: bool = False,
                  ema_decay: float = 0.0,
+                 lr_schedule: str = '',
+                 lr_schedule_params: list[str] = [],
                  **kwargs: dict[str, Any]):
         super().__init__()
         self._logger = logging.getLogger(__name__)
@@ -307,6 +310,14 @@ class SRModel(_Base):
         #: `Trainer.fit` creates the average and updates it behind every optimizer step; `ema_weights()` evaluates under it
         _ema.ParamEMA._check_decay(ema_decay)
         self.ema_decay = float(ema_decay)
+        #: learning-rate schedule (lr_sched.DeviceLRSchedule): its kind ('' : none, nothing is built or allocated) and its constants as
+        #: `name=value` strings, e.g. "cosine", ["t_max=300000", "eta_min=1e-7", "warmup_steps=2000"]; checked here, built by
+        #: `configure_optimizers()` and attached to the optimizer it returns (`optimizer.lr_schedule`)
+        self._lr_schedule = str(lr_schedule)
+        if self._lr_schedule:
+            self._lr_schedule_constants = _lr_sched.parse_params(self._lr_schedule, list(lr_schedule_params))
+        elif lr_schedule_params:
+            raise ValueError(f"lr_schedule_params {list(lr_schedule_params)} without an lr_schedule")
         #: arithmetic type of the HIP path: storage dtype of activations / packed weights (fp32 accumulate)
         self.compute_dtype = _dtype_from_precision(precision)
         #: storage dtype of the validation / predict forward.  bf16 keeps 8 mantissa bits on the residual trunk, which
@@ -333,10 +344,20 @@ class SRModel(_Base):
         `flush()` first."""
         return self.ema.swapped() if self.ema is not None else contextlib.nullcontext()
 
+    #: a `DeviceLRSchedule.state_dict()` (a checkpoint's) that the next `configure_optimizers()` loads into the schedule it builds
+    lr_schedule_state = None
+
     # -- optimizers: srmodel.py:145-154 ------------------------------------------------------------
     def configure_optimizers(self):
+        """`[optimizer]`, as the reference returns it; with `lr_schedule` the schedule is attached to it (`optimizer.lr_schedule`: it
+        advances behind every `optimizer.step()` by itself).  Call it once the model is on its device."""
         trainable = filter(lambda p: p.requires_grad, itertools.chain(self.parameters()))
-        return [self._optim(trainable, **self._optim_params)]
+        optimizer = self._optim(trainable, **self._optim_params)
+        if self._lr_schedule:
+            sched = _lr_sched.DeviceLRSchedule(optimizer, self._lr_schedule, **self._lr_schedule_constants)
+            if self.lr_schedule_state is not None:
+                sched.load_state_dict(self.lr_schedule_state)
+        return [optimizer]
 
     def forward(self, x):  # srmodel.py:156-158 (abstract)
         raise NotImplementedError

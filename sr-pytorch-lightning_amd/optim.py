@@ -12,6 +12,9 @@ table and the same kind of single launch, `srk_ranger_step`.
 `SGD` and `RMSprop` are torch.optim.SGD / torch.optim.RMSprop (`_supported_optimizers['SGD']` / `['RMSprop']`) on the same table:
 `srk_sgd_step`, `srk_rmsprop_step`.  Same constructors, `state_dict()` interchangeable with torch's in both directions.
 
+All four take `lr` by value in their launch arguments (a tensor `lr` is refused); `lr_sched.DeviceLRSchedule` makes their launches read
+it from the device instead (`lr_dev`), so that a replayed step follows a schedule.
+
 Nothing here falls back to PyTorch arithmetic: parameters must be fp32 tensors on a GPU and the HIP library must load.
 """
 import ctypes as C
@@ -159,6 +162,11 @@ class _TableStep:
     _step_key = "step"
     _entry = "srk_adam"
     _sparse_msg = "Adam does not support sparse gradients, please consider SparseAdam instead"
+    #: per parameter group the address of the device double its launches read `lr` from (`lr_dev`, include/srk.h), set by
+    #: `lr_sched.DeviceLRSchedule`; None: `lr` travels by value from `group["lr"]`
+    _lr_dev = None
+    #: the `lr_sched.DeviceLRSchedule` attached to this optimizer, if any
+    lr_schedule = None
 
     # -- state ------------------------------------------------------------------------------------
     def _keys(self, group):
@@ -287,6 +295,9 @@ class _TableStep:
             with torch.enable_grad():
                 loss = closure()
         launches = []
+        lr_dev = self._lr_dev
+        if lr_dev is not None and len(lr_dev) != len(self.param_groups):
+            raise RuntimeError("%s: a parameter group was added after the lr schedule was attached; detach() it and attach a new one" % type(self).__name__)
         for gi, group in enumerate(self.param_groups):
             plan = self._plan(gi, group)
             if plan is None:
@@ -295,7 +306,10 @@ class _TableStep:
                 t = self._table(plan, group)
                 if t.nblocks == 0:
                     continue
-                launches.append((plan, t, self._args(plan, t, group)))
+                a = self._args(plan, t, group)
+                if lr_dev is not None:
+                    a.lr_dev = lr_dev[gi]                    # read when the launch runs: a replay follows the schedule
+                launches.append((plan, t, a))
         lib, e = L.load(), self._entry
         # torch.amp.GradScaler.step looks at EVERY group's gradients before it steps any: with several groups all checks come first
         # (an inf in group 1 used to leave group 0 updated); one group keeps the combined entry point (same three launches)

@@ -334,12 +334,16 @@ class GraphedStep:
         self.failed = False
         self.hyper = None
         self.pending_hyper = None            # the hyper-parameters that were live when the pending gradients were produced
+        self.captures = 0                    # how many times the step has been captured (a hyper-parameter change re-captures)
 
     def _hyper(self):
         """The optimizer's hyper-parameters travel BY VALUE in the captured launch (srk_adam_args): a scheduler or a manual
-        change after the capture would be ignored by a replay, so a change re-captures."""
-        keys = ("lr", "betas", "eps", "weight_decay", "maximize", "momentum", "dampening", "nesterov", "alpha", "centered", "k",
+        change after the capture would be ignored by a replay, so a change re-captures.  Not `lr` under an
+        `lr_sched.DeviceLRSchedule`: the launches read it from the device when they run (`group["lr"]` stays at the base value)."""
+        keys = ("betas", "eps", "weight_decay", "maximize", "momentum", "dampening", "nesterov", "alpha", "centered", "k",
                 "N_sma_threshhold")
+        if getattr(self.opt, "_lr_dev", None) is None:
+            keys = ("lr",) + keys
         return tuple(tuple((k, tuple(g[k]) if isinstance(g[k], (tuple, list)) else float(g[k])) for k in keys if k in g)
                      for g in self.opt.param_groups)
 
@@ -394,8 +398,15 @@ class GraphedStep:
         else:
             self.opt.step(grad_scaler=self.scaler)
 
+    def _replayed(self):
+        """A graph that holds the optimizer step has been replayed: the lr schedule's captured advance ran with it."""
+        sched = getattr(self.opt, "lr_schedule", None)
+        if sched is not None:
+            sched.replayed()
+
     def _capture(self, batch):
         from . import ops
+        self.captures += 1
         self.static = {"lr": batch["lr"].clone(), "hr": batch["hr"].clone()}
         self.hyper = self._hyper()
         if hasattr(self.opt, "reserve_capture_tables"):
@@ -477,6 +488,7 @@ class GraphedStep:
             try:
                 torch.cuda.synchronize()
                 self.ogs.capture(batch)
+                self.captures += 1
                 self.static, self.graphs, self.hyper = self.ogs.static, tuple(self.ogs.graphs), self._hyper()
                 return self.ogs.step()
             except Exception as e:  # noqa: BLE001
@@ -511,6 +523,7 @@ class GraphedStep:
             self.static["lr"].copy_(batch["lr"], non_blocking=True)
             self.static["hr"].copy_(batch["hr"], non_blocking=True)
         self.graphs[0].replay()
+        self._replayed()
         if len(self.graphs) == 2:            # [pending update] forward, backward, packing were the graph; the collective is eager
             self.gsync.reduce()
             self.pending_hyper = self.hyper  # (the replay applied the previous update with the captured values and left a new one pending)
@@ -749,7 +762,7 @@ class Trainer:
         if not use_ddp and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             gsync = GradSync(model, bucket_bytes=int(os.environ.get("SRK_BUCKET_BYTES", 32 << 20)))
             gsync.broadcast()
-        optimizer = model.configure_optimizers()[0]
+        optimizer = self.optimizer = model.configure_optimizers()[0]      # (kept: its `lr_schedule`, if any, is what a checkpoint saves)
         scaler = None
         use_scaler = self.use_grad_scaler
         if use_scaler is None:
