@@ -1043,6 +1043,44 @@ typedef struct {
 } srk_lr_sched_args;
 int srk_lr_sched_step(const srk_lr_sched_args* a, srk_stream_t stream);
 
+/* ---- gradient clipping by norm and by value (grad_clip.py), csrc/grad_clip.hip ------------------------------------------------------
+ * torch.nn.utils.clip_grad_norm_ (norm_type 2) / clip_grad_value_ over the optimizers' table (srk_adam_slot: `g` the fp32 gradient,
+ * clipped IN PLACE; `p`, `state_off`, `step_idx` unused; srk_adam_block: one workgroup per block), as launches of the step itself.
+ * `state`: SRK_CLIP_STATE_FLOATS device floats, indexed by SRK_CLIP_*:
+ *     MAX_NORM, CLIP_VALUE : the thresholds, read when a launch RUNS (a replayed hipGraph follows a value written between two replays)
+ *     TOTAL_NORM, COEF     : what the last srk_grad_clip_coef computed
+ *     NUM_CLIPPED, NUM_NONFINITE : how many of its runs had coef < 1 / a norm that was not finite (floats: exact up to 2^24)
+ * `partials`: device doubles, one per block of EVERY parameter group's table; `base`: the first entry of this launch's group.
+ * `scaler_state`: NULL, or optim.DeviceGradScaler's device floats when the gradients still carry the loss scale s = scaler_state[0].
+ *   srk_grad_sumsq      (per group)  partials[base + b] = sum of g*g over block b: every element squared and added in double, thread by
+ *                        thread in one fixed element order (the same for aligned and unaligned gradients), the 256 thread sums
+ *                        combined in a fixed order.  No atomics, nothing to zero: the same gradients give the same bits.
+ *   srk_grad_clip_coef  (once)  sum = partials[0] + ... + partials[nblocks_total - 1] in double, fixed order;  norm = sqrt(sum) / s;
+ *                        coef = min(1, max_norm / (norm + 1e-6)) in double (torch's formula);  TOTAL_NORM = (float)norm,
+ *                        COEF = (float)coef;  NUM_CLIPPED += 1 if (float)coef < 1.  A norm that is not finite: COEF = 1,
+ *                        NUM_NONFINITE += 1 -- the gradients pass on unchanged (the loss scaler skips the step, or the optimizer sees them).
+ *   srk_grad_clip_apply (per group)  g *= COEF in fp32.  A workgroup that reads COEF == 1 returns before it touches the gradient.
+ *   srk_grad_clip_value (per group)  g = g < -b ? -b : (g > b ? b : g),  b = CLIP_VALUE, or (float)(CLIP_VALUE * s) in fp32 under the
+ *                        scaler; a NaN stays a NaN (torch.clamp), and under the scaler an infinite g stays infinite, so that the
+ *                        scaler's check behind this launch still finds both and skips the step (GradScaler.unscale_ records an
+ *                        overflow BEFORE torch's clip); without a scaler +-inf becomes +-b, as torch.clamp gives.
+ * Traffic per parameter: sumsq 4 B, apply 8 B (0 B when nothing is clipped), value 8 B. */
+enum { SRK_CLIP_MAX_NORM = 0, SRK_CLIP_CLIP_VALUE = 1, SRK_CLIP_TOTAL_NORM = 2, SRK_CLIP_COEF = 3, SRK_CLIP_NUM_CLIPPED = 4,
+       SRK_CLIP_NUM_NONFINITE = 5 };
+#define SRK_CLIP_STATE_FLOATS 8
+typedef struct {
+  const srk_adam_slot* slots; const srk_adam_block* blocks; int nslots, nblocks;   /* sumsq, apply, value: this group's table */
+  float* state;
+  double* partials;                         /* sumsq: written; coef: read                                      */
+  int base;                                 /* sumsq: this group's first entry of `partials`                    */
+  int nblocks_total;                        /* coef: entries of `partials` (the blocks of all groups)           */
+  const float* scaler_state;                /* coef, value: NULL, or the loss scaler's state (s = scaler_state[0]) */
+} srk_grad_clip_args;
+int srk_grad_sumsq(const srk_grad_clip_args* a, srk_stream_t stream);
+int srk_grad_clip_coef(const srk_grad_clip_args* a, srk_stream_t stream);
+int srk_grad_clip_apply(const srk_grad_clip_args* a, srk_stream_t stream);
+int srk_grad_clip_value(const srk_grad_clip_args* a, srk_stream_t stream);
+
 /* ---- tiled and self-ensemble inference (tiling.py), csrc/tile.hip -------------------------------------------------------------
  * The two data movements around the model's forward when a large image is predicted as a batch of overlapping tiles and / or as the
  * mean over the 8 flips and transposes of the input.  Transform id k: bit 0 reverses W, bit 1 reverses H, bit 2 transposes H and W

@@ -21,6 +21,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import ema as _ema
+from .. import grad_clip as _grad_clip
 from .. import lr_sched as _lr_sched
 from .. import optim as _hip_optim
 from .. import tiling as _tiling
@@ -273,6 +274,8 @@ class SRModel(_Base):
                  ema_decay: float = 0.0,
                  lr_schedule: str = '',
                  lr_schedule_params: list[str] = [],
+                 gradient_clip_val: int | float | None = None,
+                 gradient_clip_algorithm: str | None = None,
                  **kwargs: dict[str, Any]):
         super().__init__()
         self._logger = logging.getLogger(__name__)
@@ -318,6 +321,15 @@ class SRModel(_Base):
             self._lr_schedule_constants = _lr_sched.parse_params(self._lr_schedule, list(lr_schedule_params))
         elif lr_schedule_params:
             raise ValueError(f"lr_schedule_params {list(lr_schedule_params)} without an lr_schedule")
+        #: gradient clipping (grad_clip.GradClip), under Lightning's Trainer keys and defaults: `gradient_clip_val` None is off (nothing
+        #: is built or allocated), `gradient_clip_algorithm` None means "norm"; checked here, built by `configure_optimizers()` and
+        #: attached to the optimizer it returns (`optimizer._clip`)
+        self._clip_algorithm = "norm" if gradient_clip_algorithm is None else gradient_clip_algorithm
+        self._clip_val = None
+        if gradient_clip_val is not None:
+            self._clip_val, _ = _grad_clip.check_args(gradient_clip_val, self._clip_algorithm)
+        elif self._clip_algorithm not in _grad_clip.ALGORITHMS:
+            raise ValueError(f"gradient_clip_algorithm not recognized: {gradient_clip_algorithm!r}. Supported: {', '.join(_grad_clip.ALGORITHMS)}")
         #: arithmetic type of the HIP path: storage dtype of activations / packed weights (fp32 accumulate)
         self.compute_dtype = _dtype_from_precision(precision)
         #: storage dtype of the validation / predict forward.  bf16 keeps 8 mantissa bits on the residual trunk, which
@@ -346,17 +358,24 @@ class SRModel(_Base):
 
     #: a `DeviceLRSchedule.state_dict()` (a checkpoint's) that the next `configure_optimizers()` loads into the schedule it builds
     lr_schedule_state = None
+    #: a `GradClip.state_dict()` (a checkpoint's) that the next `configure_optimizers()` loads into the clipper it builds
+    grad_clip_state = None
 
     # -- optimizers: srmodel.py:145-154 ------------------------------------------------------------
     def configure_optimizers(self):
         """`[optimizer]`, as the reference returns it; with `lr_schedule` the schedule is attached to it (`optimizer.lr_schedule`: it
-        advances behind every `optimizer.step()` by itself).  Call it once the model is on its device."""
+        advances behind every `optimizer.step()` by itself), with `gradient_clip_val` the clipper (`optimizer._clip`: its launches run inside
+        `optimizer.step()`).  Call it once the model is on its device."""
         trainable = filter(lambda p: p.requires_grad, itertools.chain(self.parameters()))
         optimizer = self._optim(trainable, **self._optim_params)
         if self._lr_schedule:
             sched = _lr_sched.DeviceLRSchedule(optimizer, self._lr_schedule, **self._lr_schedule_constants)
             if self.lr_schedule_state is not None:
                 sched.load_state_dict(self.lr_schedule_state)
+        if self._clip_val is not None:
+            clip = _grad_clip.GradClip(optimizer, self._clip_val, self._clip_algorithm)
+            if self.grad_clip_state is not None:
+                clip.load_state_dict(self.grad_clip_state)
         return [optimizer]
 
     def forward(self, x):  # srmodel.py:156-158 (abstract)

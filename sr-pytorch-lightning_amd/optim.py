@@ -167,6 +167,8 @@ class _TableStep:
     _lr_dev = None
     #: the `lr_sched.DeviceLRSchedule` attached to this optimizer, if any
     lr_schedule = None
+    #: the `grad_clip.GradClip` attached to this optimizer, if any: `step()` issues its launches over the tables it has just built
+    _clip = None
 
     # -- state ------------------------------------------------------------------------------------
     def _keys(self, group):
@@ -282,12 +284,21 @@ class _TableStep:
     @torch.no_grad()
     def step(self, closure=None, grad_scaler=None):
         """grad_scaler: a `DeviceGradScaler` whose scale the gradients still carry (fp16 training): the launch checks them for
-        non-finite values, skips the whole update if it finds one, divides by the scale otherwise, and adjusts the scale."""
+        non-finite values, skips the whole update if it finds one, divides by the scale otherwise, and adjusts the scale.
+        With a `grad_clip.GradClip` attached the gradients of all groups are clipped first, in place, by launches of this call."""
         on_gpu = {p.is_cuda for group in self.param_groups for p in group["params"]}
         if on_gpu == {False}:
             if grad_scaler is not None:
                 raise RuntimeError("DeviceGradScaler needs GPU parameters")
-            return self._cpu_step(closure)
+            if self._clip is None:
+                return self._cpu_step(closure)
+            loss = None
+            if closure is not None:                          # the closure produces the gradients: it runs before they are clipped
+                with torch.enable_grad():
+                    loss = closure()
+            self._clip.clip_cpu()
+            self._cpu_step(None)
+            return loss
         if on_gpu != {True}:
             raise RuntimeError("%s: parameters on both CPU and GPU" % type(self).__name__)
         loss = None
@@ -310,6 +321,8 @@ class _TableStep:
                 if lr_dev is not None:
                     a.lr_dev = lr_dev[gi]                    # read when the launch runs: a replay follows the schedule
                 launches.append((plan, t, a))
+        if self._clip is not None:
+            self._clip.launch(launches, grad_scaler)         # over the tables built above: before every check and update
         lib, e = L.load(), self._entry
         # torch.amp.GradScaler.step looks at EVERY group's gradients before it steps any: with several groups all checks come first
         # (an inf in group 1 used to leave group 0 updated); one group keeps the combined entry point (same three launches)

@@ -339,7 +339,8 @@ class GraphedStep:
     def _hyper(self):
         """The optimizer's hyper-parameters travel BY VALUE in the captured launch (srk_adam_args): a scheduler or a manual
         change after the capture would be ignored by a replay, so a change re-captures.  Not `lr` under an
-        `lr_sched.DeviceLRSchedule`: the launches read it from the device when they run (`group["lr"]` stays at the base value)."""
+        `lr_sched.DeviceLRSchedule`: the launches read it from the device when they run (`group["lr"]` stays at the base value).  Nor
+        the thresholds of a `grad_clip.GradClip`: they live on the device too."""
         keys = ("betas", "eps", "weight_decay", "maximize", "momentum", "dampening", "nesterov", "alpha", "centered", "k",
                 "N_sma_threshhold")
         if getattr(self.opt, "_lr_dev", None) is None:
@@ -798,8 +799,11 @@ class Trainer:
                 self._loss_dev.append(loss.detach().clone())
                 if self.log_every and (step + 1) % self.log_every == 0:
                     last = self.losses[-1]
+                    clip = getattr(optimizer, "_clip", None)
+                    # (the loss read above has synchronised already; the norm is that of the last step whose update has run)
+                    norm = f", grad norm {float(clip.total_norm):.6g}" if clip is not None and clip.algorithm == "norm" else ""
                     if self.rank == 0:
-                        print(f"step {step + 1}: loss {last:.6f}", flush=True)
+                        print(f"step {step + 1}: loss {last:.6f}{norm}", flush=True)
                 elif len(self._loss_dev) >= 1024:
                     self.losses  # noqa: B018  (drain to the host list)
             if graphed is not None:

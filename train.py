@@ -39,13 +39,16 @@ def parse(argv=None):
     p.add_argument("--default_root_dir", default=".")
     p.add_argument("--checkpoint", default=None, help="state_dict (.pt / Lightning .ckpt) to start from")
     p.add_argument("--save", default=None, help="where rank 0 writes {'state_dict': ...} at the end (with --ema_decay also 'state_dict_ema' and 'ema_num_updates', "
-                   "with --lr_schedule also 'lr_schedule')")
+                   "with --lr_schedule also 'lr_schedule', with --gradient_clip_val also 'grad_clip')")
     p.add_argument("--ema_decay", type=float, default=0.0, help="decay of the exponential moving average of the weights, e.g. 0.999 (0: off); "
                    "validation and 'state_dict_ema' use the averaged weights")
     p.add_argument("--lr_schedule", default="", help="learning-rate schedule, advanced once per optimizer step on the device: constant, step, "
                    "multistep, cosine, cosine_restarts (default: none)")
     p.add_argument("--lr_schedule_params", nargs="*", default=[], help="its constants as name=value, e.g. t_max=300000 eta_min=1e-7 "
                    "warmup_steps=2000; step_size=200000 gamma=0.5; milestones=200000,400000 gamma=0.5")
+    p.add_argument("--gradient_clip_val", type=float, default=None, help="clip the gradients inside every optimizer step (Lightning Trainer key; "
+                   "default: off): the threshold of the total 2-norm, or of each element with --gradient_clip_algorithm value")
+    p.add_argument("--gradient_clip_algorithm", default=None, choices=("norm", "value"), help="norm (default) or value (Lightning Trainer key)")
     p.add_argument("--train_dir", default=None, help="directory of HR training images (default: synthetic patches)")
     p.add_argument("--val_dir", default=None, help="directory of HR validation images")
     p.add_argument("--eval_datasets", nargs="+", default=None)
@@ -92,13 +95,16 @@ def main(argv=None):
         kw["eval_datasets"] = [os.path.basename(os.path.normpath(a.val_dir))]
     model = cls(scale_factor=a.scale_factor, patch_size=a.patch_size, batch_size=a.batch_size, precision=a.precision,
                 losses=a.losses, optimizer=a.optimizer, default_root_dir=a.default_root_dir, devices=a.devices, ema_decay=a.ema_decay,
-                lr_schedule=a.lr_schedule, lr_schedule_params=a.lr_schedule_params, **kw)
+                lr_schedule=a.lr_schedule, lr_schedule_params=a.lr_schedule_params, gradient_clip_val=a.gradient_clip_val,
+                gradient_clip_algorithm=a.gradient_clip_algorithm, **kw)
     sd = None
     if a.checkpoint:
         sd = torch.load(a.checkpoint, map_location="cpu")
         model.load_state_dict(sd.get("state_dict", sd), strict=True)
     if a.lr_schedule and sd is not None and "lr_schedule" in sd:
         model.lr_schedule_state = sd["lr_schedule"]          # the schedule fit() builds continues at the checkpoint's count
+    if a.gradient_clip_val is not None and sd is not None and "grad_clip" in sd:
+        model.grad_clip_state = sd["grad_clip"]              # the clipper fit() builds continues with the checkpoint's value and counters
     tr = T.Trainer(device="cuda" if use_gpu else "cpu", max_steps=a.max_steps, log_every=a.log_every)
     if a.ema_decay > 0 and sd is not None and "state_dict_ema" in sd:
         # a checkpoint that carries an average restores it (on the device the weights train on); without one fit() starts the
@@ -157,6 +163,9 @@ def main(argv=None):
         sched = getattr(getattr(tr, "optimizer", None), "lr_schedule", None)
         if sched is not None:
             ckpt["lr_schedule"] = sched.state_dict()
+        clip = getattr(getattr(tr, "optimizer", None), "_clip", None)
+        if clip is not None:
+            ckpt["grad_clip"] = clip.state_dict()
         torch.save(ckpt, a.save)
     if tr.rank == 0 and tr.losses:
         print(f"done: {len(tr.losses)} steps, last loss {tr.losses[-1]:.6f}", flush=True)
