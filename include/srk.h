@@ -639,6 +639,70 @@ int srk_gmsd_fwd(const srk_gmsd_args* a, srk_stream_t stream);
 int srk_gmsd_finalize(const srk_gmsd_args* a, srk_stream_t stream);
 int srk_gmsd_bwd(const srk_gmsd_args* a, srk_stream_t stream);
 
+/* ---- pixel losses: Charbonnier, Huber, smooth-L1, Barron's general robust loss with fixed alpha and c, and the PSNR loss,
+ * csrc/pixel_loss.hip.  d = sr - hr, nothing is clamped, mean reduction; hr gets no gradient.
+ * Elementwise family, `kind` (uniform per launch: the kernels are instantiated per kind, no per-element branch on it), parameters p0, p1:
+ *   CHARBONNIER   sqrt(d^2 + p0^2)                                         psi = d / sqrt(d^2 + p0^2)            p0 = eps
+ *   HUBER         |d| <= p0 ? d^2 / 2 : p0 (|d| - p0 / 2)                  psi = |d| <= p0 ? d : p0 sign(d)      p0 = delta
+ *   SMOOTH_L1     |d| <  p0 ? d^2 / (2 p0) : |d| - p0 / 2                  psi = |d| <  p0 ? d / p0 : sign(d)    p0 = beta (0: L1)
+ *   ROBUST_*      rho(d; alpha, c) of Barron (CVPR 2019, eq. 13), z = (d / c)^2, b = |alpha - 2|, p0 = alpha, p1 = c; the host picks
+ *                 the exact case:  _A2 (alpha = 2): z / 2;  _A0 (alpha = 0): log1p(z / 2);  _NEG_INF: -expm1(-z / 2);
+ *                 _GENERAL (any other alpha): (b / alpha) expm1((alpha / 2) log1p(z / b)), the form that does not cancel in
+ *                 fp32 for small |d|;  psi = (d / c^2) (z / b + 1)^(alpha / 2 - 1) and its limits d / c^2, (d / c^2) / (z / 2 + 1),
+ *                 (d / c^2) exp(-z / 2).  The kinds are told apart on the fp32 alpha this struct carries; _GENERAL needs alpha, b,
+ *                 1 / b and b / alpha, and every robust kind c^2 and 1 / c^2, to be finite normal fp32 numbers (the caller's check).
+ * Forward: float4 grid-stride loads of both images, per thread an fp32 sum of at most four values, then double; wave shuffle + LDS;
+ * one double per block in its own slot (no atomics), a scalar tail for n % 4; srk_l1_loss_mean over the srk_pixel_loss_blocks(n)
+ * partials gives the loss.  Backward: grad = (*gout) * scale * psi(d), gout a DEVICE scalar (no host sync, capturable), psi
+ * RECOMPUTED from the two saved images: forward moves 8 B per element, backward 12 B, and nothing HR-sized is allocated besides
+ * grad (storing psi in the forward would move 12 B and 8 B, the same 20 B, and hold one more HR-sized buffer from forward to
+ * backward).  sr, hr and grad 16-byte aligned. */
+enum { SRK_PIXEL_CHARBONNIER = 0, SRK_PIXEL_HUBER = 1, SRK_PIXEL_SMOOTH_L1 = 2, SRK_PIXEL_ROBUST_A2 = 3, SRK_PIXEL_ROBUST_A0 = 4,
+       SRK_PIXEL_ROBUST_NEG_INF = 5, SRK_PIXEL_ROBUST_GENERAL = 6 };
+#define SRK_PIXEL_LOSS_BLOCK_ELEMS 1024
+#define SRK_PIXEL_LOSS_BLOCKS_MAX 2048
+typedef struct srk_pixel_loss_args {
+  const float* sr;                        /* [n] (forward, backward)                                                          */
+  const float* hr;                        /* [n] (forward, backward)                                                          */
+  long long n;
+  int kind;                               /* SRK_PIXEL_*                                                                      */
+  float p0, p1;                           /* the kind's parameters (above); an unused one is ignored                          */
+  double* partial;                        /* forward: [srk_pixel_loss_blocks(n)] partial sums                                 */
+  const float* gout;                      /* backward: device scalar                                                          */
+  float scale;                            /* backward: 1 / n                                                                  */
+  float* grad;                            /* backward: [n] d loss / d sr                                                      */
+} srk_pixel_loss_args;
+/* blocks of either launch, the length of `partial`: ceil(floor(n / 4) / 256), the float4s over the 256 threads of a block, kept in
+ * [1, SRK_PIXEL_LOSS_BLOCKS_MAX] (n = 1025 is one block: the grid-stride loop and block 0's tail cover every element) */
+int srk_pixel_loss_blocks(long long n);
+int srk_pixel_loss_fwd(const srk_pixel_loss_args* a, srk_stream_t stream);
+int srk_pixel_loss_bwd(const srk_pixel_loss_args* a, srk_stream_t stream);
+
+/* PSNR loss (NAFNet's PSNRLoss on RGB): loss = (10 / ln 10) mean_n ln(mse_n + eps), mse_n the mean of d^2 over the `per` = C H W
+ * elements of image n: minus the PSNR in dB.  Forward: block (n, b) of a grid that flattens (image, block) into ONE dimension (more
+ * than 65,535 images work) writes the fp64 sum of d^2 over its share of image n into slot n * (blocks per image) + b.  An image starts
+ * at element n * per of a 16-byte-aligned tensor, so its first (-n per) mod 4 elements and its last ones are read as scalars and the
+ * float4 loads in between never hold another image's pixel.  Finalize: one workgroup, fixed order: mse_n, coef[n] = (10 / ln 10) / N
+ * * 2 / (per (mse_n + eps)), the loss.  Backward: grad = ((*gout) * coef[n]) * d, 12 B per element.  An image equal to its target gives
+ * ln(eps) and a zero gradient.  N * (blocks per image) < 2^24: a grid of fewer than 2^32 threads, which is what HIP launches. */
+typedef struct srk_psnr_loss_args {
+  const float* sr;                        /* [N][per] (forward, backward)                                                     */
+  const float* hr;                        /* [N][per] (forward, backward)                                                     */
+  int N;
+  long long per;                          /* elements per image, C * H * W                                                    */
+  float eps;
+  double* partial;                        /* [srk_psnr_loss_blocks(N, per)]: per (image, block) sum of d^2                    */
+  float* coef;                            /* [N]: finalize writes, backward reads                                             */
+  float* loss;                            /* finalize: device scalar                                                          */
+  const float* gout;                      /* backward: device scalar                                                          */
+  float* grad;                            /* backward: [N][per] d loss / d sr                                                 */
+} srk_psnr_loss_args;
+/* blocks of the forward and the backward grid, N * (blocks per image), or -1 when the sizes are refused (N or per < 1, 2^24 blocks or more) */
+long long srk_psnr_loss_blocks(int N, long long per);
+int srk_psnr_loss_fwd(const srk_psnr_loss_args* a, srk_stream_t stream);
+int srk_psnr_loss_finalize(const srk_psnr_loss_args* a, srk_stream_t stream);
+int srk_psnr_loss_bwd(const srk_psnr_loss_args* a, srk_stream_t stream);
+
 /* ---- SSIM with piq.ssim's defaults (reference srmodel.py:52-53,567-593 -> piq.ssim): images are average-pooled by
  * `pool` = max(1, round(min(H, W) / 256)) (floor division of the extent, as F.avg_pool2d), filtered with the separable
  * 11-tap Gaussian (sigma), and the SSIM map of the VALID region ((Hp-10) x (Wp-10)) is summed per (image, channel)

@@ -11,6 +11,7 @@ Out of scope: perceptual / adaptive losses, Co
 TensorBoard image dumps, model-parallel flags (accepted and ignored with a warning).
 """
 import contextlib
+import functools
 import itertools
 import logging
 from dataclasses import dataclass
@@ -108,8 +109,22 @@ def _gmsd_loss(sr, hr):
     return gmsd.gmsd_loss(sr, hr)
 
 
+def _pixel_loss(name):
+    """The pixel losses of pixel_loss.py (BasicSR's CharbonnierLoss and PSNRLoss, torch's HuberLoss and SmoothL1Loss, Barron's robust
+    loss with fixed alpha and c), called on sr as it comes (no clamp, like l1): fn(sr, hr, **parameters); on the GPU the fused HIP
+    forward/backward (pixel_loss.PixelLossFn / PSNRLossFn), elsewhere pixel_loss.pixel_loss_torch.  `_create_losses` binds the
+    parameters that `loss_params` gives."""
+    def fn(sr, hr, **params):
+        from .. import pixel_loss
+        return getattr(pixel_loss, f"{name}_loss")(sr, hr, **params)
+    fn.__name__ = f"_{name}_loss"
+    return fn
+
+
+_pixel_losses = ("charbonnier", "huber", "smooth_l1", "robust", "psnr")
 _supported_losses = {"l1": _l1_loss, "l2": F.mse_loss, "mae": _l1_loss, "mse": F.mse_loss, "flip": _flip_loss,
-                     "haarpsi": _haarpsi_loss, "ssim": _ssim_loss, "ms_ssim": _ms_ssim_loss, "gmsd": _gmsd_loss}
+                     "haarpsi": _haarpsi_loss, "ssim": _ssim_loss, "ms_ssim": _ms_ssim_loss, "gmsd": _gmsd_loss,
+                     **{name: _pixel_loss(name) for name in _pixel_losses}}
 _MS_SSIM_MIN_PATCH = 161          # ops_metrics.MS_SSIM_MIN_SIZE: (11 - 1) * 2^4 + 1
 _out_of_scope_losses = {"adaptive", "dists", "edge_loss", "lpips", "pencil_sketch", "pieapp"}
 
@@ -276,6 +291,7 @@ class SRModel(_Base):
                  lr_schedule_params: list[str] = [],
                  gradient_clip_val: int | float | None = None,
                  gradient_clip_algorithm: str | None = None,
+                 loss_params: list[str] = [],
                  **kwargs: dict[str, Any]):
         super().__init__()
         self._logger = logging.getLogger(__name__)
@@ -293,7 +309,7 @@ class SRModel(_Base):
         self._last_epoch = max_epochs
         self._log_loss_every_n_epochs = log_loss_every_n_epochs
         self._log_weights_every_n_epochs = log_weights_every_n_epochs
-        self._losses = self._create_losses(losses, patch_size, precision)
+        self._losses = self._create_losses(losses, patch_size, precision, loss_params)
         self._metrics = self._create_metrics(metrics)
         if channels != 3 and ("flip" in {l.name for l in self._losses} or "FLIP" in {m for m, _ in self._metrics}):
             raise ValueError(f"the FLIP loss / metric compares colours and needs channels == 3 (got channels={channels})")
@@ -511,7 +527,9 @@ class SRModel(_Base):
         return state
 
     # -- srmodel.py:435-501 ------------------------------------------------------------------------------
-    def _create_losses(self, losses_str: str, patch_size: int, precision=32) -> list[_SubLoss]:
+    def _create_losses(self, losses_str: str, patch_size: int, precision=32, loss_params=()) -> list[_SubLoss]:
+        """`loss_params`: the pixel losses' parameters as `<loss>.<key>=<value>` strings (pixel_loss.pixel_loss_parse_params), e.g.
+        ["charbonnier.eps=1e-6", "robust.alpha=-2", "robust.c=0.05"]; an entry must name a loss of `losses_str`."""
         losses = []
         for loss in losses_str.split('+'):
             loss_split = loss.split('*')
@@ -536,6 +554,12 @@ class SRModel(_Base):
                 raise ValueError(f'loss ms_ssim needs an HR patch of at least {_MS_SSIM_MIN_PATCH} (five levels of an 11-tap filter), '
                                  f'got patch_size={patch_size}')
             losses.append(_SubLoss(name=loss_type, loss=fn, weight=weight))
+        if loss_params or any(l.name in _pixel_losses for l in losses):
+            from ..pixel_loss import pixel_loss_parse_params
+            params = pixel_loss_parse_params([l.name for l in losses], list(loss_params))
+            for l in losses:
+                if l.name in params:
+                    l.loss = functools.partial(l.loss, **params[l.name])
         return losses
 
     def _create_metrics(self, metrics: list[str]):

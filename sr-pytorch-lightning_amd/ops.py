@@ -1511,3 +1511,4 @@ from .haarpsi import *       # noqa: E402,F401,F403  HaarPSI loss (csrc/haarpsi.
 from .ssim_loss import *     # noqa: E402,F401,F403  SSIM loss (csrc/ssim_loss.hip)
 from .ms_ssim_loss import *  # noqa: E402,F401,F403  MS-SSIM loss (csrc/ms_ssim_loss.hip)
 from .gmsd import *          # noqa: E402,F401,F403  GMSD loss and metric (csrc/gmsd.hip)
+from .pixel_loss import *    # noqa: E402,F401,F403  Charbonnier, Huber, smooth-L1, robust and PSNR losses (csrc/pixel_loss.hip)

@@ -28,7 +28,10 @@ def parse(argv=None):
     p.add_argument("--patch_size", type=int, default=128, help="HR patch edge (LR = patch_size // scale_factor)")
     p.add_argument("--batch_size", type=int, default=16)
     p.add_argument("--precision", default="bf16", help="32, 16 or bf16 (Trainer key of the reference)")
-    p.add_argument("--losses", default="l1", help="loss or weighted composite, e.g. l1, \"0.9*l1+0.1*flip\", \"0.9*l1+0.1*haarpsi\", \"0.16*l1+0.84*ssim\", \"0.16*l1+0.84*ms_ssim\" (--patch_size >= 161), \"0.9*l1+0.1*gmsd\"")
+    p.add_argument("--losses", default="l1", help="loss or weighted composite, e.g. l1, \"0.9*l1+0.1*flip\", \"0.9*l1+0.1*haarpsi\", \"0.16*l1+0.84*ssim\", \"0.16*l1+0.84*ms_ssim\" (--patch_size >= 161), \"0.9*l1+0.1*gmsd\"; "
+                   "the pixel terms charbonnier, huber, smooth_l1, robust (needs --loss_params robust.alpha=... robust.c=...) and psnr, e.g. \"0.5*l1+0.5*charbonnier\"")
+    p.add_argument("--loss_params", nargs="*", default=[], help="parameters of the pixel losses as <loss>.<key>=<value>, e.g. charbonnier.eps=1e-6 "
+                   "huber.delta=0.5 smooth_l1.beta=0.1 robust.alpha=-2 robust.c=0.05 psnr.eps=1e-8")
     p.add_argument("--metrics", nargs="+", default=None, help="validation metrics (default: the model's, PSNR SSIM); e.g. PSNR SSIM MS-SSIM FLIP GMSD")
     p.add_argument("--optimizer", default="ADAM")
     p.add_argument("--max_steps", type=int, default=100)
@@ -96,7 +99,7 @@ def main(argv=None):
     model = cls(scale_factor=a.scale_factor, patch_size=a.patch_size, batch_size=a.batch_size, precision=a.precision,
                 losses=a.losses, optimizer=a.optimizer, default_root_dir=a.default_root_dir, devices=a.devices, ema_decay=a.ema_decay,
                 lr_schedule=a.lr_schedule, lr_schedule_params=a.lr_schedule_params, gradient_clip_val=a.gradient_clip_val,
-                gradient_clip_algorithm=a.gradient_clip_algorithm, **kw)
+                gradient_clip_algorithm=a.gradient_clip_algorithm, loss_params=a.loss_params, **kw)
     sd = None
     if a.checkpoint:
         sd = torch.load(a.checkpoint, map_location="cpu")
