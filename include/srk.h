@@ -703,6 +703,64 @@ int srk_psnr_loss_fwd(const srk_psnr_loss_args* a, srk_stream_t stream);
 int srk_psnr_loss_finalize(const srk_psnr_loss_args* a, srk_stream_t stream);
 int srk_psnr_loss_bwd(const srk_psnr_loss_args* a, srk_stream_t stream);
 
+/* ---- frequency losses: the FFT loss (BasicSR's FFTLoss) and the focal frequency loss (Jiang et al., ICCV 2021), csrc/freq_loss.hip.
+ * d = sr - hr, nothing clamped; per plane (n, c) of H x W the full unnormalised spectrum D[k][l] = sum_{h,w} d[h][w]
+ * e^{-2 pi i (k h / H + l w / W)}.  At the self-conjugate bins (2k = 0 mod H and 2l = 0 mod W) Im D IS 0 (d is real): every kernel sets
+ * it to 0 there and never keeps a rounding residue; its sign is 0 in the gradient.
+ *   fft   L = (sum |Re D| + sum |Im D|) / (2 N C H W);  d L / d d = Re(F^H G) / (2 N C H W), G = sign(Re D) + i sign(Im D)
+ *   ffl   q = |D|^2 / (H W), w = (q / q_max)^(alpha / 2) with q_max the plane's maximum, w a constant of the gradient;
+ *         L = sum w q / (N C H W);  d L / d D = 2 w D / (H W) / (N C H W);  a plane with q_max = 0 gives loss 0 and gradient 0
+ * The transform is a direct matrix DFT on the fp32 matrix pipe (v_mfma_f32_32x32x2_f32: exact fp32).  d is real, so row H - k of the
+ * spectrum is the conjugate of row k read backwards: only the rows k = 0 .. H / 2 are computed; the rows with 0 < 2k < H count twice, k = 0 and
+ * (H even) k = H / 2 once.  The value is that of the full spectrum.
+ * Twiddles: tw_h = [2][H] (cos, then sin, of 2 pi m / H, m = 0 .. H - 1; built in double, rounded to fp32 once), tw_w = [2][W]; the
+ * kernels index them with (j k) mod n, formed with integers, and never call a sine or cosine.
+ * Forward: one workgroup per (plane, block of 32 rows k): T = Fh[k block] d (32 x W complex, LDS; sr and hr are read here, once
+ * per block), then D = T Fw per 32 columns in accumulators, the elementwise term on the accumulators, and per workgroup TWO doubles
+ * in its own slot: (sum, max q) -- fft: sum of |Re D| + |Im D|, max unused (0); ffl: sum of q^(1 + alpha / 2), max of q.  The spectrum
+ * never reaches memory.  Finalize: one workgroup, fixed order, double: per plane the sum of its blocks (ffl: over q_max^(alpha / 2),
+ * and q_max to `qmax`), then the sum over planes and the division.  Backward, two launches: (1) the same workgroups recompute D, form
+ * G in place (fft: the signs; ffl: 2 w D / (H W) with `qmax`), weight it by the row's count and apply the adjoint along the rows,
+ * V = G Fw^H, written to `scratch`; (2) one workgroup per (plane, 32 columns): grad = Re(Fh^H V) * scale * (*gout), every element
+ * written once.  No atomics, no host sync; hr gets no gradient.  NCHW fp32 contiguous, 1 <= H, W <= 512, 0 <= alpha <= 8 (beyond
+ * that q^(1 + alpha / 2) leaves fp32 on images far outside [0, 1]: the caller computes in torch). */
+#define SRK_FREQ_MAX_SIZE 512
+#define SRK_FREQ_MAX_ALPHA 8
+typedef struct srk_fft_loss_args {
+  const float* sr;                        /* [N][C][H][W] (forward, backward)                                                  */
+  const float* hr;                        /* [N][C][H][W] (forward, backward)                                                  */
+  int N, C, H, W;
+  const float* tw_h;                      /* [2][H]: cos, sin of 2 pi m / H                                                    */
+  const float* tw_w;                      /* [2][W]: cos, sin of 2 pi m / W                                                    */
+  double* partial;                        /* [srk_freq_loss_tiles(N, C, H, W)][2]: per workgroup (sum, 0)                      */
+  float* loss;                            /* finalize: device scalar                                                           */
+  float* scratch;                         /* backward: [N C][2][H / 2 + 1][W], written by its first launch, read by its second */
+  const float* gout;                      /* backward: device scalar                                                           */
+  float* grad;                            /* backward: [N][C][H][W] d loss / d sr                                              */
+} srk_fft_loss_args;
+typedef struct srk_ffl_loss_args {
+  const float* sr;                        /* [N][C][H][W] (forward, backward)                                                  */
+  const float* hr;                        /* [N][C][H][W] (forward, backward)                                                  */
+  int N, C, H, W;
+  float alpha;                            /* 0 <= alpha <= SRK_FREQ_MAX_ALPHA                                                  */
+  const float* tw_h;                      /* [2][H]: cos, sin of 2 pi m / H                                                    */
+  const float* tw_w;                      /* [2][W]: cos, sin of 2 pi m / W                                                    */
+  double* partial;                        /* [srk_freq_loss_tiles(N, C, H, W)][2]: per workgroup (sum q^(1 + alpha / 2), max q) */
+  float* qmax;                            /* [N C]: finalize writes each plane's largest q, backward reads                     */
+  float* loss;                            /* finalize: device scalar                                                           */
+  float* scratch;                         /* backward: [N C][2][H / 2 + 1][W], written by its first launch, read by its second */
+  const float* gout;                      /* backward: device scalar                                                           */
+  float* grad;                            /* backward: [N][C][H][W] d loss / d sr                                              */
+} srk_ffl_loss_args;
+/* workgroups of the forward over the whole batch, N C ceil((H / 2 + 1) / 32): the rows of `partial`; -1 when the sizes are refused */
+int srk_freq_loss_tiles(int N, int C, int H, int W);
+int srk_fft_loss_fwd(const srk_fft_loss_args* a, srk_stream_t stream);
+int srk_fft_loss_finalize(const srk_fft_loss_args* a, srk_stream_t stream);
+int srk_fft_loss_bwd(const srk_fft_loss_args* a, srk_stream_t stream);
+int srk_ffl_loss_fwd(const srk_ffl_loss_args* a, srk_stream_t stream);
+int srk_ffl_loss_finalize(const srk_ffl_loss_args* a, srk_stream_t stream);
+int srk_ffl_loss_bwd(const srk_ffl_loss_args* a, srk_stream_t stream);
+
 /* ---- SSIM with piq.ssim's defaults (reference srmodel.py:52-53,567-593 -> piq.ssim): images are average-pooled by
  * `pool` = max(1, round(min(H, W) / 256)) (floor division of the extent, as F.avg_pool2d), filtered with the separable
  * 11-tap Gaussian (sigma), and the SSIM map of the VALID region ((Hp-10) x (Wp-10)) is summed per (image, channel)

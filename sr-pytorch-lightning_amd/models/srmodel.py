@@ -121,10 +121,26 @@ def _pixel_loss(name):
     return fn
 
 
+def _fft_loss(sr, hr):
+    """BasicSR's FFTLoss (the L1 of the 2-D spectrum; NAFSSR's and MIMO-UNet's `l1 + 0.01..0.1 * fft`), called on sr as it comes
+    (no clamp, like l1).  UNNORMALISED like BasicSR's: its weight scales with sqrt(H W) of the HR patch.  On the GPU the fused HIP
+    forward/backward (freq_loss.FFTLossFn), elsewhere freq_loss.fft_loss_torch."""
+    from .. import freq_loss
+    return freq_loss.fft_loss(sr, hr)
+
+
+def _ffl_loss(sr, hr, **params):
+    """The focal frequency loss (Jiang et al., ICCV 2021; patch_factor=1, no averaging, no log), called on sr as it comes;
+    `loss_params` gives `ffl.alpha` (default 1).  On the GPU the fused HIP forward/backward (freq_loss.FFLLossFn), elsewhere
+    freq_loss.ffl_loss_torch."""
+    from .. import freq_loss
+    return freq_loss.ffl_loss(sr, hr, **params)
+
+
 _pixel_losses = ("charbonnier", "huber", "smooth_l1", "robust", "psnr")
 _supported_losses = {"l1": _l1_loss, "l2": F.mse_loss, "mae": _l1_loss, "mse": F.mse_loss, "flip": _flip_loss,
                      "haarpsi": _haarpsi_loss, "ssim": _ssim_loss, "ms_ssim": _ms_ssim_loss, "gmsd": _gmsd_loss,
-                     **{name: _pixel_loss(name) for name in _pixel_losses}}
+                     **{name: _pixel_loss(name) for name in _pixel_losses}, "fft": _fft_loss, "ffl": _ffl_loss}
 _MS_SSIM_MIN_PATCH = 161          # ops_metrics.MS_SSIM_MIN_SIZE: (11 - 1) * 2^4 + 1
 _out_of_scope_losses = {"adaptive", "dists", "edge_loss", "lpips", "pencil_sketch", "pieapp"}
 
@@ -529,7 +545,8 @@ class SRModel(_Base):
     # -- srmodel.py:435-501 ------------------------------------------------------------------------------
     def _create_losses(self, losses_str: str, patch_size: int, precision=32, loss_params=()) -> list[_SubLoss]:
         """`loss_params`: the pixel losses' parameters as `<loss>.<key>=<value>` strings (pixel_loss.pixel_loss_parse_params), e.g.
-        ["charbonnier.eps=1e-6", "robust.alpha=-2", "robust.c=0.05"]; an entry must name a loss of `losses_str`."""
+        ["charbonnier.eps=1e-6", "robust.alpha=-2", "robust.c=0.05"], and the focal frequency loss's `ffl.alpha=...`
+        (freq_loss.freq_loss_parse_params); an entry must name a loss of `losses_str`."""
         losses = []
         for loss in losses_str.split('+'):
             loss_split = loss.split('*')
@@ -554,9 +571,16 @@ class SRModel(_Base):
                 raise ValueError(f'loss ms_ssim needs an HR patch of at least {_MS_SSIM_MIN_PATCH} (five levels of an 11-tap filter), '
                                  f'got patch_size={patch_size}')
             losses.append(_SubLoss(name=loss_type, loss=fn, weight=weight))
-        if loss_params or any(l.name in _pixel_losses for l in losses):
+        names = [l.name for l in losses]
+        if loss_params or any(name in _pixel_losses or name == "ffl" for name in names):
+            from ..freq_loss import freq_loss_parse_params
             from ..pixel_loss import pixel_loss_parse_params
-            params = pixel_loss_parse_params([l.name for l in losses], list(loss_params))
+            # ffl's entries are its own (its alpha obeys another rule than robust's); every other entry, `fft.x=...` and an `ffl....`
+            # without the loss among them, is refused where it always was
+            own = [e for e in loss_params if "ffl" in names and str(e).strip().lower().partition(".")[0].strip() == "ffl"]
+            params = pixel_loss_parse_params(names, [e for e in loss_params if e not in own])
+            if "ffl" in names:
+                params.update(freq_loss_parse_params(own))
             for l in losses:
                 if l.name in params:
                     l.loss = functools.partial(l.loss, **params[l.name])

@@ -1512,3 +1512,4 @@ from .ssim_loss import *     # noqa: E402,F401,F403  SSIM loss (csrc/ssim_loss.h
 from .ms_ssim_loss import *  # noqa: E402,F401,F403  MS-SSIM loss (csrc/ms_ssim_loss.hip)
 from .gmsd import *          # noqa: E402,F401,F403  GMSD loss and metric (csrc/gmsd.hip)
 from .pixel_loss import *    # noqa: E402,F401,F403  Charbonnier, Huber, smooth-L1, robust and PSNR losses (csrc/pixel_loss.hip)
+from .freq_loss import *     # noqa: E402,F401,F403  FFT and focal frequency losses (csrc/freq_loss.hip)

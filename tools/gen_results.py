@@ -247,6 +247,21 @@ def block(tag, short=False):
     return "\n".join(out) + "\n"
 
 
+def freq_loss_block():
+    """The table of INTEGRATION.md "Frequency losses" from the JSON lines of profiles/freq_loss.txt (tools/microbench_freq_loss.py)."""
+    rows = [json.loads(line) for line in (_text("freq_loss.txt") or "").splitlines() if line.startswith("{")]
+    out = ["| loss | shape | HIP fwd+bwd, us (min - max) | eager forms fwd+bwd, us | fastest eager / HIP | peak memory of a step, MiB: HIP / eager |",
+           "|---|---|---|---|---|---|"]
+    for r in rows:
+        forms = [k[len("eager_"):-len("_us")] for k in r if k.startswith("eager_") and k.endswith("_us") and "min_max" not in k]
+        eager = ", ".join(f"{f}: {r[f'eager_{f}_us']:,.0f}" for f in forms)
+        mem = " / ".join([f"{r['hip_peak_MiB']:,.0f}"] + [f"{r[f'eager_{f}_peak_MiB']:,.0f}" for f in forms])
+        lo, hi = r["hip_min_max_us"]
+        out.append(f"| `{r['loss']}` | {r['shape']} | {r['hip_fwd_bwd_us']:,.0f} ({lo:,.0f} - {hi:,.0f}) | {eager} | "
+                   f"{r['ratio_fastest_eager_over_hip']:.2f} | {mem} |")
+    return "\n".join(out) + "\n"
+
+
 def main():
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     tag = args[0] if args else "r6"
@@ -254,8 +269,9 @@ def main():
     b, e = f"<!-- results:{tag}:begin -->\n", f"<!-- results:{tag}:end -->"
     bad = 0
     first = os.path.join(ROOT, "DESIGN.md") if tag == "r6" else os.path.join(P, "HISTORY.md")      # earlier rounds' results live in profiles/HISTORY.md
-    for path in (first, os.path.join(P, "README.md")):
-        body = block(tag, short=(path.endswith("DESIGN.md")))
+    # tag freq_loss: one block, in INTEGRATION.md (tests/test_freq_loss_cpu.py checks it)
+    for path in ((os.path.join(ROOT, "INTEGRATION.md"),) if tag == "freq_loss" else (first, os.path.join(P, "README.md"))):
+        body = freq_loss_block() if tag == "freq_loss" else block(tag, short=(path.endswith("DESIGN.md")))
         s = open(path).read()
         if b not in s or e not in s:
             print(f"{path}: markers for {tag} not found")
