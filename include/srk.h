@@ -1203,6 +1203,28 @@ int srk_grad_clip_coef(const srk_grad_clip_args* a, srk_stream_t stream);
 int srk_grad_clip_apply(const srk_grad_clip_args* a, srk_stream_t stream);
 int srk_grad_clip_value(const srk_grad_clip_args* a, srk_stream_t stream);
 
+/* ---- gradient accumulation over micro-batches (grad_accum.py), csrc/grad_accum.hip ------------------------------------------------
+ * One launch over the optimizers' table: srk_adam_slot (`g` the fp32 gradient of this micro-step, `state_off` the tensor's offset in
+ * floats into the flat fp32 `acc` buffer -- the layout of the optimizers' flat state; `p`, `step_idx` unused) and srk_adam_block (one
+ * workgroup per block).  A window is k micro-steps; `acc` is all zeros at its start.  `op`:
+ *     SRK_ACCUM_ADD   (micro-steps 1 .. k-1) : acc = acc + g
+ *     SRK_ACCUM_FINAL (micro-step k)         : g = (acc + g) * inv_k;  acc = 0
+ * `inv_k` = (float)(1.0 / k), formed in double by the host and passed BY VALUE, 0 < inv_k <= 1 (ADD does not read it).  All fp32, every
+ * operation rounded on its own, not contracted: for k a power of two the result is bit for bit what `(loss / k).backward()` k times
+ * leaves in `.grad`; for other k it differs by roundings.  FINAL writes the mean IN PLACE of the gradient, where clipping and the
+ * optimizers read it, and zeroes `acc` for the next window.  Non-finite values are not special-cased: an inf or NaN of any micro-step
+ * reaches the final g (the loss scaler's check behind FINAL then skips the window's update), and `acc` is still zeroed.  Which op runs is
+ * the HOST's choice (which hipGraph it replays): nothing on the device counts micro-steps.
+ * Traffic: 12 B per parameter (ADD), 16 B (FINAL). */
+enum { SRK_ACCUM_ADD = 0, SRK_ACCUM_FINAL = 1 };
+typedef struct {
+  const srk_adam_slot* slots; const srk_adam_block* blocks; int nslots, nblocks;
+  float* acc;
+  float inv_k;
+  int op;
+} srk_grad_accum_args;
+int srk_grad_accum(const srk_grad_accum_args* a, srk_stream_t stream);
+
 /* ---- tiled and self-ensemble inference (tiling.py), csrc/tile.hip -------------------------------------------------------------
  * The two data movements around the model's forward when a large image is predicted as a batch of overlapping tiles and / or as the
  * mean over the 8 flips and transposes of the input.  Transform id k: bit 0 reverses W, bit 1 reverses H, bit 2 transposes H and W

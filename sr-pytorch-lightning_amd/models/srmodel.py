@@ -22,6 +22,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import ema as _ema
+from .. import grad_accum as _grad_accum
 from .. import grad_clip as _grad_clip
 from .. import lr_sched as _lr_sched
 from .. import optim as _hip_optim
@@ -307,6 +308,7 @@ class SRModel(_Base):
                  lr_schedule_params: list[str] = [],
                  gradient_clip_val: int | float | None = None,
                  gradient_clip_algorithm: str | None = None,
+                 accumulate_grad_batches: int = 1,
                  loss_params: list[str] = [],
                  **kwargs: dict[str, Any]):
         super().__init__()
@@ -362,6 +364,10 @@ class SRModel(_Base):
             self._clip_val, _ = _grad_clip.check_args(gradient_clip_val, self._clip_algorithm)
         elif self._clip_algorithm not in _grad_clip.ALGORITHMS:
             raise ValueError(f"gradient_clip_algorithm not recognized: {gradient_clip_algorithm!r}. Supported: {', '.join(_grad_clip.ALGORITHMS)}")
+        #: gradient accumulation (grad_accum.GradAccum), Lightning's Trainer key: the optimizer steps once per window of this many batches, on
+        #: the mean of their gradients; 1 is off (nothing is built or allocated).  Checked here, built by `configure_optimizers()` and
+        #: attached to the optimizer it returns (`optimizer._accum`)
+        self._accumulate_grad_batches = _grad_accum.check_args(accumulate_grad_batches)
         #: arithmetic type of the HIP path: storage dtype of activations / packed weights (fp32 accumulate)
         self.compute_dtype = _dtype_from_precision(precision)
         #: storage dtype of the validation / predict forward.  bf16 keeps 8 mantissa bits on the residual trunk, which
@@ -397,7 +403,8 @@ class SRModel(_Base):
     def configure_optimizers(self):
         """`[optimizer]`, as the reference returns it; with `lr_schedule` the schedule is attached to it (`optimizer.lr_schedule`: it
         advances behind every `optimizer.step()` by itself), with `gradient_clip_val` the clipper (`optimizer._clip`: its launches run inside
-        `optimizer.step()`).  Call it once the model is on its device."""
+        `optimizer.step()`), with `accumulate_grad_batches` > 1 the accumulator (`optimizer._accum`: callers step through its `step()`).  Call it
+        once the model is on its device."""
         trainable = filter(lambda p: p.requires_grad, itertools.chain(self.parameters()))
         optimizer = self._optim(trainable, **self._optim_params)
         if self._lr_schedule:
@@ -408,6 +415,8 @@ class SRModel(_Base):
             clip = _grad_clip.GradClip(optimizer, self._clip_val, self._clip_algorithm)
             if self.grad_clip_state is not None:
                 clip.load_state_dict(self.grad_clip_state)
+        if self._accumulate_grad_batches > 1:
+            _grad_accum.GradAccum(optimizer, self._accumulate_grad_batches)
         return [optimizer]
 
     def forward(self, x):  # srmodel.py:156-158 (abstract)

@@ -145,6 +145,7 @@ class _Plan:
         self.device = None
         self.steps = self.ticket = None  # per-parameter update counts (torch counts per parameter)
         self.cap = 0
+        self.size = 0           # floats of every flat buffer (what `grad_accum.GradAccum` sizes its own by)
         self.eager = None       # _Table of the launch-by-launch steps
         self.captured = []      # _Tables owned by hipGraph captures: written once, kept alive as long as the plan
         self.spare = None       # allocated OUTSIDE any capture (page-locked allocations are not capturable) for the next one
@@ -169,6 +170,9 @@ class _TableStep:
     lr_schedule = None
     #: the `grad_clip.GradClip` attached to this optimizer, if any: `step()` issues its launches over the tables it has just built
     _clip = None
+    #: the `grad_accum.GradAccum` attached to this optimizer, if any: `accumulate()` adds the gradients to its buffers, `step()` turns them
+    #: into the window's mean before anything else reads them
+    _accum = None
 
     # -- state ------------------------------------------------------------------------------------
     def _keys(self, group):
@@ -200,8 +204,8 @@ class _TableStep:
         for k, p in enumerate(params):
             plan.offsets[p], plan.index[p] = off, k
             off += (p.numel() + 3) // 4 * 4                 # every tensor starts 16-byte aligned
-        plan.keys, plan.device = keys, dev
-        plan.flat = {key: torch.zeros(max(off, 4), dtype=torch.float32, device=dev) for key in keys}
+        plan.keys, plan.device, plan.size = keys, dev, max(off, 4)
+        plan.flat = {key: torch.zeros(plan.size, dtype=torch.float32, device=dev) for key in keys}
         plan.m, plan.v = plan.flat.get("exp_avg"), plan.flat.get("exp_avg_sq")
         plan.steps = torch.zeros(len(params), dtype=torch.float32, device=dev)
         plan.ticket = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -246,6 +250,8 @@ class _TableStep:
             plan = self._plan(gi, group)
             if plan is not None and plan.spare is None:
                 plan.spare = _Table(plan.cap, plan.device)
+        if self._accum is not None:
+            self._accum.reserve(self._plans)
 
     def release_captured_tables(self):
         """Call after the graphs that captured this optimizer's step have been destroyed (a re-capture): their tables are
@@ -281,30 +287,9 @@ class _TableStep:
         return t.fill([(p, g, plan.offsets[p], plan.index[p]) for p, g in live], key, capturing)
 
     # -- step -------------------------------------------------------------------------------------
-    @torch.no_grad()
-    def step(self, closure=None, grad_scaler=None):
-        """grad_scaler: a `DeviceGradScaler` whose scale the gradients still carry (fp16 training): the launch checks them for
-        non-finite values, skips the whole update if it finds one, divides by the scale otherwise, and adjusts the scale.
-        With a `grad_clip.GradClip` attached the gradients of all groups are clipped first, in place, by launches of this call."""
-        on_gpu = {p.is_cuda for group in self.param_groups for p in group["params"]}
-        if on_gpu == {False}:
-            if grad_scaler is not None:
-                raise RuntimeError("DeviceGradScaler needs GPU parameters")
-            if self._clip is None:
-                return self._cpu_step(closure)
-            loss = None
-            if closure is not None:                          # the closure produces the gradients: it runs before they are clipped
-                with torch.enable_grad():
-                    loss = closure()
-            self._clip.clip_cpu()
-            self._cpu_step(None)
-            return loss
-        if on_gpu != {True}:
-            raise RuntimeError("%s: parameters on both CPU and GPU" % type(self).__name__)
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
+    def _launches(self):
+        """(group index, plan, table, launch arguments) of every parameter group that has gradients: the device tables of this call
+        (`_table`: the eager one, or a fresh one owned by the capture in progress) and what the group's update is launched with."""
         launches = []
         lr_dev = self._lr_dev
         if lr_dev is not None and len(lr_dev) != len(self.param_groups):
@@ -320,7 +305,55 @@ class _TableStep:
                 a = self._args(plan, t, group)
                 if lr_dev is not None:
                     a.lr_dev = lr_dev[gi]                    # read when the launch runs: a replay follows the schedule
-                launches.append((plan, t, a))
+                launches.append((gi, plan, t, a))
+        return launches
+
+    @torch.no_grad()
+    def accumulate(self):
+        """A micro-step that is not the last of its window (`grad_accum.GradAccum`): the gradients are added to the accumulator's
+        buffers over the same tables `step()` builds, and nothing else happens -- it is not `step()`, so no step hook fires (the EMA and
+        the lr schedule stay where they are), nothing is clipped, checked or updated."""
+        if self._accum is None:
+            raise RuntimeError("%s.accumulate() needs a grad_accum.GradAccum attached" % type(self).__name__)
+        on_gpu = {p.is_cuda for group in self.param_groups for p in group["params"]}
+        if on_gpu == {False}:
+            return self._accum.apply_cpu(L.SRK_ACCUM_ADD)
+        if on_gpu != {True}:
+            raise RuntimeError("%s: parameters on both CPU and GPU" % type(self).__name__)
+        self._accum.launch([(gi, plan, t) for gi, plan, t, _ in self._launches()], L.SRK_ACCUM_ADD)
+
+    @torch.no_grad()
+    def step(self, closure=None, grad_scaler=None):
+        """grad_scaler: a `DeviceGradScaler` whose scale the gradients still carry (fp16 training): the launch checks them for
+        non-finite values, skips the whole update if it finds one, divides by the scale otherwise, and adjusts the scale.
+        With a `grad_clip.GradClip` attached the gradients of all groups are clipped first, in place, by launches of this call; with a
+        `grad_accum.GradAccum` they are first of all replaced by the mean over the window this call ends (SRK_ACCUM_FINAL)."""
+        on_gpu = {p.is_cuda for group in self.param_groups for p in group["params"]}
+        if on_gpu == {False}:
+            if grad_scaler is not None:
+                raise RuntimeError("DeviceGradScaler needs GPU parameters")
+            if self._clip is None and self._accum is None:
+                return self._cpu_step(closure)
+            loss = None
+            if closure is not None:                          # the closure produces the gradients: it runs before they are averaged and clipped
+                with torch.enable_grad():
+                    loss = closure()
+            if self._accum is not None:
+                self._accum.apply_cpu(L.SRK_ACCUM_FINAL)
+            if self._clip is not None:
+                self._clip.clip_cpu()
+            self._cpu_step(None)
+            return loss
+        if on_gpu != {True}:
+            raise RuntimeError("%s: parameters on both CPU and GPU" % type(self).__name__)
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        launches = self._launches()
+        if self._accum is not None:                          # the window's mean gradient, in place: before clipping and every check and update
+            self._accum.launch([(gi, plan, t) for gi, plan, t, _ in launches], L.SRK_ACCUM_FINAL)
+        launches = [(plan, t, a) for _, plan, t, a in launches]
         if self._clip is not None:
             self._clip.launch(launches, grad_scaler)         # over the tables built above: before every check and update
         lib, e = L.load(), self._entry

@@ -248,6 +248,19 @@ def _eager_fwd_bwd_reduce(model, net, optimizer, gsync, scaler, batch):
     return loss.detach()
 
 
+def _opt_step(optimizer, scaler=None):
+    """The optimizer's part of a training step: `optimizer.step(...)`, or with a `grad_accum.GradAccum` attached its `step(...)`, which
+    accumulates on all but the last micro-step of a window.  Returns whether the optimizer stepped."""
+    accum = getattr(optimizer, "_accum", None)
+    if accum is not None:
+        return accum.step(grad_scaler=scaler)
+    if scaler is None:
+        optimizer.step()
+    else:
+        optimizer.step(grad_scaler=scaler)
+    return True
+
+
 def _eager_step(model, net, optimizer, gsync, scaler, batch):
     """forward -> losses -> backward -> [gradient average] -> optimizer step, launch by launch."""
     from . import ops
@@ -260,7 +273,7 @@ def _eager_step(model, net, optimizer, gsync, scaler, batch):
         ops.flush_wgrads()
         if gsync is not None:
             gsync.sync()
-        optimizer.step(grad_scaler=scaler)
+        _opt_step(optimizer, scaler)
     elif scaler is not None:                                  # torch.amp.GradScaler (an optimizer that is not one of optim.py's)
         scaler.scale(loss).backward()
         ops.flush_wgrads()
@@ -273,7 +286,7 @@ def _eager_step(model, net, optimizer, gsync, scaler, batch):
         ops.flush_wgrads()               # normally a no-op: the engine's final callback already ran
         if gsync is not None:
             gsync.sync()
-        optimizer.step()
+        _opt_step(optimizer)
     # detached: an autograd graph of an eager step that is still referenced when a later step is CAPTURED gets released inside
     # the capture (when its holder is reassigned), which crashes hipStreamEndCapture on this stack
     return loss.detach()
@@ -316,6 +329,10 @@ class GraphedStep:
     no collective is ever inside a capture.  Round 4's form of it: ONE graph = [the update of the PREVIOUS step] + forward + backward +
     packing, so between two calls the parameters LAG one update; `flush()` applies it (call it before anything reads the parameters:
     validation, checkpoints; `finish()` at the end of training), always with the hyper-parameters its gradients were produced under.
+    With a `grad_accum.GradAccum` on the optimizer there is one such set of graphs per phase -- "accumulate" (the micro-step adds its
+    gradients to the accumulator) and "step" (it ends the window: FINAL, clipping, the update, the EMA, the schedule) -- each captured
+    the first time its phase comes up after the warm-up (`captures` ends at 2), sharing the static input buffers; which one is replayed
+    is the host's choice (`accum.phase`), and several ranks keep the one-graph form, whose opening micro-step is the pending gradients'.
     A batch of another shape (a short last batch) runs eagerly.  If a capture fails
     the loop stays eager (and says so once).  Callers must not keep a loss WITH its autograd graph from an earlier eager step
     alive across the capture (`_eager_step` returns it detached for that reason)."""
@@ -325,7 +342,11 @@ class GraphedStep:
         self.scaler = scaler                 # optim.DeviceGradScaler (fp16) or None: its launches are part of the captured step
         self.pending = False                 # several ranks, graph form: reduced gradients whose optimizer step opens the NEXT replay
         self.warm_steps = int(warm_steps)
-        self.segments = auto_segments(model) if gsync is not None else 1
+        # grad_accum.GradAccum, if any: one set of graphs per phase ("accumulate" / "step"), chosen on the host before every replay;
+        # several ranks then keep the one-graph form (no segmented backward)
+        self.accum = getattr(optimizer, "_accum", None)
+        self.by_phase = {}                   # phase -> (graphs, static loss tensor), with an accumulator only
+        self.segments = auto_segments(model) if gsync is not None and self.accum is None else 1
         self.ogs = None                      # OverlappedGraphStep (several ranks, large models): all-reduces beside backward
         self.seen = 0
         self.graphs = None
@@ -394,10 +415,7 @@ class GraphedStep:
         return loss
 
     def _opt_step(self):
-        if self.scaler is None:
-            self.opt.step()
-        else:
-            self.opt.step(grad_scaler=self.scaler)
+        return _opt_step(self.opt, self.scaler)
 
     def _replayed(self):
         """A graph that holds the optimizer step has been replayed: the lr schedule's captured advance ran with it."""
@@ -408,7 +426,11 @@ class GraphedStep:
     def _capture(self, batch):
         from . import ops
         self.captures += 1
-        self.static = {"lr": batch["lr"].clone(), "hr": batch["hr"].clone()}
+        if self.by_phase:                    # the other phase's graph reads the same static inputs
+            self.static["lr"].copy_(batch["lr"], non_blocking=True)
+            self.static["hr"].copy_(batch["hr"], non_blocking=True)
+        else:
+            self.static = {"lr": batch["lr"].clone(), "hr": batch["hr"].clone()}
         self.hyper = self._hyper()
         if hasattr(self.opt, "reserve_capture_tables"):
             self.opt.reserve_capture_tables()    # page-locked staging buffers cannot be allocated inside the capture
@@ -423,6 +445,15 @@ class GraphedStep:
                 self.loss = self._fwd_bwd()
                 self._opt_step()
             self.graphs = (g,)
+        elif self.accum is not None and self.pending:
+            # the second phase comes up with the previous batch's reduced gradients pending: their micro-step opens this graph as it
+            # will open every replay of it; nothing is primed, the caller replays the graph for this batch right away
+            ga = torch.cuda.CUDAGraph()
+            with ops.graph_capture(ga, stream=side, capture_error_mode=cem):
+                self._opt_step()
+                self.loss = self._fwd_bwd()
+                self.gsync.pack()
+            self.graphs = (ga, "opt_first")
         else:
             # ONE graph per step: [optimizer step on the gradients the previous step reduced] + forward + backward + packing; only the
             # bucket all-reduces are issued eagerly between two replays (round 3 also issued the optimizer step's three launches
@@ -453,17 +484,27 @@ class GraphedStep:
 
     def __call__(self, batch):
         self.seen += 1
+        accum = self.accum
+        if accum is not None:
+            # what the graph of this call holds: this batch's micro-step (one process), or the pending gradients' (several ranks) --
+            # either way the accumulator's next
+            phase = accum.phase
+            self.graphs, self.loss = self.by_phase.get(phase, (None, None))
         same = self.static is not None and batch["lr"].shape == self.static["lr"].shape and batch["hr"].shape == self.static["hr"].shape
-        if self.failed or self.seen <= self.warm_steps or (self.graphs is not None and not same):
+        if self.failed or self.seen <= self.warm_steps or ((self.graphs is not None or self.by_phase) and not same):
             if self.ogs is not None and self.ogs.gsync is not None:
                 return self.ogs.eager_step(batch)          # (the buckets were re-cut along the segments: its own eager form)
             if self.pending:                               # optimizer-first graph form: keep "reduced gradients, update pending" invariant
                 return self.shifted_eager_step(batch)
             return _eager_step(self.model, self.net, self.opt, self.gsync, self.scaler, batch)
-        if self.graphs is not None and self._hyper() != self.hyper:
+        if (self.graphs is not None or self.by_phase) and self._hyper() != self.hyper:
             # lr / betas / ... changed: capture again with the new values (the old graphs go first, then the tables they read).  The
-            # update still pending belongs to the OLD values (`flush`, called by `_capture`)
-            self.graphs = None
+            # update still pending belongs to the OLD values (`flush`, called by `_capture`; with an accumulator here, so that both
+            # phases are captured afresh from "nothing pending")
+            if accum is not None:
+                self.flush()
+                phase = accum.phase
+            self.graphs, self.by_phase = None, {}
             if self.ogs is not None:
                 self.ogs.graphs = None
             if hasattr(self.opt, "release_captured_tables"):
@@ -511,20 +552,27 @@ class GraphedStep:
                 from . import ops
                 ops.discard_wgrads()
                 print(f"[trainer] hipGraph capture failed ({type(e).__name__}: {e}); training continues eagerly", file=sys.stderr)
-                self.failed, self.graphs, self.static = True, None, None
+                self.failed, self.graphs, self.static, self.by_phase = True, None, None, {}
                 torch.cuda.synchronize()
                 primed, self.primed = getattr(self, "primed", None), None
                 self.flush()
                 if primed is not None:       # the batch already trained eagerly up to its reduce inside _capture: its update was the flush
                     return primed
                 return _eager_step(self.model, self.net, self.opt, self.gsync, self.scaler, batch)
+            if accum is not None:
+                self.by_phase[phase] = (self.graphs, self.loss)
             if now is not None:              # several ranks: this batch trained eagerly up to the reduce; its update opens the first replay
                 return now
         else:
             self.static["lr"].copy_(batch["lr"], non_blocking=True)
             self.static["hr"].copy_(batch["hr"], non_blocking=True)
         self.graphs[0].replay()
-        self._replayed()
+        if accum is None:
+            self._replayed()
+        else:
+            if phase == "step":              # only a graph that holds a real step holds the schedule's advance
+                self._replayed()
+            accum.replayed()
         if len(self.graphs) == 2:            # [pending update] forward, backward, packing were the graph; the collective is eager
             self.gsync.reduce()
             self.pending_hyper = self.hyper  # (the replay applied the previous update with the captured values and left a new one pending)
@@ -732,7 +780,9 @@ class Trainer:
     """`fit(model, batches)`: forward -> losses -> backward -> optimizer.step, DDP when WORLD_SIZE > 1.
 
     Mirrors what Lightning's fit loop does around `SRModel.training_step` (srmodel.py:160-171):
-    nothing else (no checkpointing / loggers -- out of scope)."""
+    nothing else (no checkpointing / loggers -- out of scope).  With the model's
+    `accumulate_grad_batches` = k > 1 the optimizer steps once per window of k batches (grad_accum.GradAccum): `max_steps` and
+    `log_every` count optimizer steps, `losses` keeps one entry per batch, and a window the batches leave incomplete is dropped."""
 
     def __init__(self, device=None, max_steps=-1, log_every=0, use_grad_scaler=None, use_graph=None):
         if device is None:
@@ -783,11 +833,14 @@ class Trainer:
         if ema is not None and ema.device != next(model.parameters()).device:
             raise RuntimeError(f"the model's EMA lives on {ema.device}, its parameters on {next(model.parameters()).device}: call make_ema() after .to(device)")
         ema_hook = EmaAfterStep(optimizer, ema) if ema is not None else None
+        accum = getattr(optimizer, "_accum", None)       # grad_accum.GradAccum: the optimizer steps once per window of k batches
+        k = accum.k if accum is not None else 1
         graphed = None
         if self.use_graph and (scaler is None or hasattr(scaler, "state")) and self.device.type == "cuda" and not use_ddp:
             graphed = GraphedStep(model, net, optimizer, gsync, warm_steps=11 if gsync is not None else 3, scaler=scaler)
         try:
-            for step, batch in enumerate(batches):
+            for seen, batch in enumerate(batches):
+                step = seen // k             # optimizer steps so far (Lightning's global_step): `max_steps` and `log_every` count these
                 if 0 <= self.max_steps <= step:
                     break
                 batch = {k: (v.to(self.device, non_blocking=True) if torch.is_tensor(v) else v) for k, v in batch.items()}
@@ -797,6 +850,10 @@ class Trainer:
                     loss = _eager_step(model, net, optimizer, gsync, scaler, batch)
                 # a replayed step returns the graph's static loss tensor: clone (one tiny asynchronous launch), never float()
                 self._loss_dev.append(loss.detach().clone())
+                if (seen + 1) % k:           # a micro-step inside a window
+                    if len(self._loss_dev) >= 1024:
+                        self.losses  # noqa: B018
+                    continue
                 if self.log_every and (step + 1) % self.log_every == 0:
                     last = self.losses[-1]
                     clip = getattr(optimizer, "_clip", None)
@@ -808,6 +865,8 @@ class Trainer:
                     self.losses  # noqa: B018  (drain to the host list)
             if graphed is not None:
                 graphed.finish()         # (multi-rank graph form: the last replay's update)
+            if accum is not None:
+                accum.reset()            # a window the batches left incomplete is dropped
         finally:                 # whatever ended the loop: nothing stays attached to the parameters, the deferral switch is what it was
             self.graphed = graphed
             if ema_hook is not None:

@@ -262,6 +262,30 @@ def freq_loss_block():
     return "\n".join(out) + "\n"
 
 
+def grad_accum_block():
+    """The table of INTEGRATION.md "Gradient accumulation" from the per-model JSON lines of profiles/grad_accum.txt
+    (tools/microbench_grad_accum.py)."""
+    rows = [json.loads(line) for line in (_text("grad_accum.txt") or "").splitlines() if line.startswith("{")]
+    out = ["| parameter table | tensors / parameters | EMA update (12 B, the yardstick), us | `SRK_ACCUM_ADD` (12 B), us (min - max) | ADD / EMA | "
+           "`SRK_ACCUM_FINAL` (16 B), us (min - max) | FINAL / EMA |",
+           "|---|---|---|---|---|---|---|"]
+    for r in rows:
+        if "accum_add_us" not in r:
+            continue
+        (alo, ahi), (flo, fhi) = r["accum_add_min_max_us"], r["accum_final_min_max_us"]
+        out.append(f"| `{r['model']}` | {r['tensors']} / {r['parameters']:,} | {r['ema_update_us']:.2f} | {r['accum_add_us']:.2f} ({alo:.2f} - {ahi:.2f}) | "
+                   f"{r['add_over_ema']:.3f} | {r['accum_final_us']:.2f} ({flo:.2f} - {fhi:.2f}) | {r['final_over_ema']:.3f} |")
+    for r in rows:
+        if "accumulate_graph_us" in r:
+            out.append("")
+            out.append(f"Replay of one small training step (`{r['model']}`, batch {r['batch']}, k = {r['k']}): accumulate-phase graph "
+                       f"{r['accumulate_graph_us']:.1f} us, step-phase graph {r['step_graph_us']:.1f} us.")
+    return "\n".join(out) + "\n"
+
+
+INTEGRATION_BLOCKS = {"freq_loss": freq_loss_block, "grad_accum": grad_accum_block}
+
+
 def main():
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     tag = args[0] if args else "r6"
@@ -269,9 +293,9 @@ def main():
     b, e = f"<!-- results:{tag}:begin -->\n", f"<!-- results:{tag}:end -->"
     bad = 0
     first = os.path.join(ROOT, "DESIGN.md") if tag == "r6" else os.path.join(P, "HISTORY.md")      # earlier rounds' results live in profiles/HISTORY.md
-    # tag freq_loss: one block, in INTEGRATION.md (tests/test_freq_loss_cpu.py checks it)
-    for path in ((os.path.join(ROOT, "INTEGRATION.md"),) if tag == "freq_loss" else (first, os.path.join(P, "README.md"))):
-        body = freq_loss_block() if tag == "freq_loss" else block(tag, short=(path.endswith("DESIGN.md")))
+    # tags freq_loss, grad_accum: one block each, in INTEGRATION.md (tests/test_freq_loss_cpu.py, tests/test_grad_accum_cpu.py check them)
+    for path in ((os.path.join(ROOT, "INTEGRATION.md"),) if tag in INTEGRATION_BLOCKS else (first, os.path.join(P, "README.md"))):
+        body = INTEGRATION_BLOCKS[tag]() if tag in INTEGRATION_BLOCKS else block(tag, short=(path.endswith("DESIGN.md")))
         s = open(path).read()
         if b not in s or e not in s:
             print(f"{path}: markers for {tag} not found")

@@ -53,6 +53,8 @@ def parse(argv=None):
     p.add_argument("--gradient_clip_val", type=float, default=None, help="clip the gradients inside every optimizer step (Lightning Trainer key; "
                    "default: off): the threshold of the total 2-norm, or of each element with --gradient_clip_algorithm value")
     p.add_argument("--gradient_clip_algorithm", default=None, choices=("norm", "value"), help="norm (default) or value (Lightning Trainer key)")
+    p.add_argument("--accumulate_grad_batches", type=int, default=1, help="step the optimizer once per this many batches, on the mean of their "
+                   "gradients (Lightning Trainer key; default 1: off); --max_steps and --log_every count optimizer steps")
     p.add_argument("--train_dir", default=None, help="directory of HR training images (default: synthetic patches)")
     p.add_argument("--val_dir", default=None, help="directory of HR validation images")
     p.add_argument("--eval_datasets", nargs="+", default=None)
@@ -79,6 +81,8 @@ def spawn(a):
 
 def main(argv=None):
     a = parse(argv)
+    if a.accumulate_grad_batches < 1:
+        raise SystemExit(f"--accumulate_grad_batches {a.accumulate_grad_batches} (must be an integer >= 1)")
     if a.devices > 1 and "WORLD_SIZE" not in os.environ:
         spawn(a)
     import torch
@@ -100,7 +104,8 @@ def main(argv=None):
     model = cls(scale_factor=a.scale_factor, patch_size=a.patch_size, batch_size=a.batch_size, precision=a.precision,
                 losses=a.losses, optimizer=a.optimizer, default_root_dir=a.default_root_dir, devices=a.devices, ema_decay=a.ema_decay,
                 lr_schedule=a.lr_schedule, lr_schedule_params=a.lr_schedule_params, gradient_clip_val=a.gradient_clip_val,
-                gradient_clip_algorithm=a.gradient_clip_algorithm, loss_params=a.loss_params, **kw)
+                gradient_clip_algorithm=a.gradient_clip_algorithm, accumulate_grad_batches=a.accumulate_grad_batches,
+                loss_params=a.loss_params, **kw)
     sd = None
     if a.checkpoint:
         sd = torch.load(a.checkpoint, map_location="cpu")
@@ -125,19 +130,20 @@ def main(argv=None):
 
         def batches():
             step, epoch = 0, 0
-            while a.max_steps < 0 or step < a.max_steps:
+            total = a.max_steps * a.accumulate_grad_batches     # batches: a window of them per optimizer step
+            while a.max_steps < 0 or step < total:
                 mine = D.shard_indices(len(pairs), tr.rank, tr.world, shuffle=True, seed=0, epoch=epoch)
                 for i in range(0, len(mine), a.batch_size):
                     yield sampler.batch(mine[i:i + a.batch_size])
                     step += 1
-                    if 0 <= a.max_steps <= step:
+                    if 0 <= a.max_steps and total <= step:
                         return
                 epoch += 1
                 if 0 <= a.max_epochs <= epoch:
                     return
         data = batches()
     else:
-        n = a.max_steps if a.max_steps >= 0 else 100
+        n = (a.max_steps if a.max_steps >= 0 else 100) * a.accumulate_grad_batches
         data = (T.synthetic_batch(a.batch_size, 3, lr_edge, a.scale_factor, 1234 + 7919 * s + tr.rank, "cpu") for s in range(n))
     tr.fit(model, data)
 
