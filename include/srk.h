@@ -1256,6 +1256,81 @@ typedef struct {
 int srk_tile_gather(const srk_tile_args* a, srk_stream_t stream);
 int srk_tile_place(const srk_tile_args* a, srk_stream_t stream);
 
+/* ---- VGG perceptual loss: the glue around srk_conv2d (vgg_loss.py), csrc/vgg_loss.hip ----------------------------------------------
+ * Replaces VGGLoss (losses/losses.py:54-117) around its torchvision feature stack: the 3x3 conv + ReLU layers themselves are srk_conv2d
+ * launches on frozen packs; these are the passes between them.  All activations are DENSE NHWC in the storage dtype (`dtype`), channels
+ * a multiple of 16, so every lane moves 16-byte channel chunks.  No atomics anywhere: every result is bit-identical run to run.
+ *   srk_vgg_prepare   : sr and hr ([N][3][H][W] fp32) -> ONE tensor [2N][H][W][16], images 0..N-1 from sr, N..2N-1 from hr;
+ *                       channel c < 3 is (x - mean_c) / std_c in fp32 (ImageNet's mean 0.485, 0.456, 0.406 and std 0.229, 0.224,
+ *                       0.225), rounded once; channels 3..15 are zero.  Nothing is clamped.  hr NULL: sr alone, [N][H][W][16].
+ *   srk_vgg_pool_fwd  : nn.MaxPool2d(2, 2): y[n][i][j][c] = max of x[n][2i..2i+1][2j..2j+1][c], Ho = H / 2, Wo = W / 2 (floor: an odd
+ *                       last row / column is dropped).  H, W >= 2.
+ *   srk_vgg_pool_bwd  : its backward in GATHER form: gx[n][y][x][c] = gy[n][y/2][x/2][c] when x[n][y][x][c] is the FIRST maximum of its
+ *                       window in row-major order (torch's rule) and, with relu_mask, x[n][y][x][c] > 0 (x is a post-ReLU activation:
+ *                       the gradient then is the one with respect to the pre-activation); 0 otherwise and in a dropped row / column.
+ *   srk_vgg_feat_fwd  : per workgroup, in a fixed slot, the double sum of (fs - fh)^2 (criterion SRK_VGG_L2) or |fs - fh| (SRK_VGG_L1)
+ *                       over its share of the n elements of two feature maps; every difference is formed and summed in double.
+ *   srk_vgg_feat_finalize : one workgroup: the partials in a fixed order, loss = rescale * sum / n (fp32).
+ *   srk_vgg_feat_grad : gf = (fs > 0) ? (fs - fh  |  sign(fs - fh)) : 0 in the storage dtype: the UN-normalised gradient with respect to
+ *                       the last pre-activation.  The backward chain is linear, so the factor it lacks is applied at its end:
+ *   srk_vgg_image_grad: g [N][H][W][16] (the data gradient of the first conv) -> grad [N][3][H][W] fp32,
+ *                       grad = g[c] * (*gout * scale) / std_c with scale = rescale * (2 | 1) / n from the host and gout the upstream
+ *                       gradient ON THE DEVICE (a term's weight and the loss scaler's scale arrive through it: capturable).
+ * Grids: srk_vgg_blocks(chunks) workgroups of 256 lanes, at most SRK_VGG_BLOCKS_MAX, each walking 16-byte chunks (prepare and
+ * image_grad: pixels) with the grid's stride; `partial` has srk_vgg_blocks(n * sizeof(elem) / 16) doubles. */
+#define SRK_VGG_BLOCKS_MAX 2048
+enum { SRK_VGG_L2 = 0, SRK_VGG_L1 = 1 };
+int srk_vgg_blocks(long long chunks);
+typedef struct {
+  const float* sr; const float* hr;         /* [N][3][H][W] fp32; hr nullable                                 */
+  void* dst;                                /* [2N][H][W][16]                                                 */
+  int N, H, W;
+  int dtype;
+} srk_vgg_prepare_args;
+int srk_vgg_prepare(const srk_vgg_prepare_args* a, srk_stream_t stream);
+/* srk_vgg_relu: x = max(x, 0) in place over n dense elements (n a multiple of 16).  fp32 storage runs a conv of the stack as several
+ * srk_conv2d launches over slices of its input channels that add up through `res` (short fp32 chains instead of one of 9 x Cin terms:
+ * the accuracy of a blocked sum); the ReLU, which srk_conv2d applies BEFORE `res`, then follows as this pass. */
+typedef struct {
+  void* x;
+  long long n;
+  int dtype;
+} srk_vgg_relu_args;
+int srk_vgg_relu(const srk_vgg_relu_args* a, srk_stream_t stream);
+typedef struct {
+  const void* x;                            /* [N][H][W][C]: the pool's input                                 */
+  void* y;                                  /* fwd out [N][H/2][W/2][C]                                       */
+  const void* gy;                           /* bwd in  [N][H/2][W/2][C]                                       */
+  void* gx;                                 /* bwd out [N][H][W][C]                                           */
+  int N, H, W, C;                           /* C a multiple of 16                                             */
+  int relu_mask;                            /* bwd                                                            */
+  int dtype;
+} srk_vgg_pool_args;
+int srk_vgg_pool_fwd(const srk_vgg_pool_args* a, srk_stream_t stream);
+int srk_vgg_pool_bwd(const srk_vgg_pool_args* a, srk_stream_t stream);
+typedef struct {
+  const void* fs; const void* fh;           /* n elements each (n a multiple of 16)                           */
+  long long n;
+  double* partial;                          /* fwd: written; finalize: read                                   */
+  float* loss;                              /* finalize                                                       */
+  float rescale;                            /* finalize                                                       */
+  int criterion;
+  void* gf;                                 /* grad out, n elements                                           */
+  int dtype;
+} srk_vgg_feat_args;
+int srk_vgg_feat_fwd(const srk_vgg_feat_args* a, srk_stream_t stream);
+int srk_vgg_feat_finalize(const srk_vgg_feat_args* a, srk_stream_t stream);
+int srk_vgg_feat_grad(const srk_vgg_feat_args* a, srk_stream_t stream);
+typedef struct {
+  const void* g;                            /* [N][H][W][16]                                                  */
+  const float* gout;                        /* the upstream gradient, one float on the device                 */
+  float* grad;                              /* [N][3][H][W] fp32                                              */
+  float scale;
+  int N, H, W;
+  int dtype;
+} srk_vgg_image_grad_args;
+int srk_vgg_image_grad(const srk_vgg_image_grad_args* a, srk_stream_t stream);
+
 /* ---- misc ------------------------------------------------------------------------------------------ */
 const char* srk_last_error(void);
 /* Name of the kernel family the calling thread launched last through srk_conv2d, srk_conv2d_wgrad or srk_unfold_nchw ("" before the

@@ -7,8 +7,8 @@ metric table.  Lightning is optional: when `lightning.pytorch` is importable the
 derives from `LightningModule` (so the reference's `main.py` / Trainer can drive it);
 otherwise from `nn.Module` with no-op logging hooks and `trainer.py`'s own fit loop.
 
-Out of scope: perceptual / adaptive losses, Comet /
-TensorBoard image dumps, model-parallel flags (accepted and ignored with a warning).
+Out of scope: the learned perceptual losses (lpips, dists,
+pieapp; `vgg` is built: vgg_loss.py) and the adaptive one, Comet / TensorBoard image dumps, model-parallel flags (accepted and ignored with a warning).
 """
 import contextlib
 import functools
@@ -138,10 +138,20 @@ def _ffl_loss(sr, hr, **params):
     return freq_loss.ffl_loss(sr, hr, **params)
 
 
+def _vgg_loss(sr, hr, **params):
+    """VGGLoss (losses/losses.py:54-117; the reference's commented `'vgg'` hook): rescale * the MSE (or L1) between the features of a
+    FROZEN VGG-19 / VGG-16 slice of sr as it comes (no clamp) and of hr.  `loss_params` gives `vgg.weights` (required: a state-dict
+    file; nothing is downloaded), `vgg.net`, `vgg.layer`, `vgg.rescale`, `vgg.criterion`, `vgg.precision`.  `_create_losses` puts a
+    `vgg_loss.VGGLoss` that owns the weights in this function's place; called directly it builds one per call.  On the GPU the HIP
+    feature stack (vgg_loss.VGGLossFn), elsewhere vgg_loss.vgg_loss_torch."""
+    from .. import vgg_loss
+    return vgg_loss.VGGLoss(**params)(sr, hr)
+
+
 _pixel_losses = ("charbonnier", "huber", "smooth_l1", "robust", "psnr")
 _supported_losses = {"l1": _l1_loss, "l2": F.mse_loss, "mae": _l1_loss, "mse": F.mse_loss, "flip": _flip_loss,
                      "haarpsi": _haarpsi_loss, "ssim": _ssim_loss, "ms_ssim": _ms_ssim_loss, "gmsd": _gmsd_loss,
-                     **{name: _pixel_loss(name) for name in _pixel_losses}, "fft": _fft_loss, "ffl": _ffl_loss}
+                     **{name: _pixel_loss(name) for name in _pixel_losses}, "vgg": _vgg_loss, "fft": _fft_loss, "ffl": _ffl_loss}
 _MS_SSIM_MIN_PATCH = 161          # ops_metrics.MS_SSIM_MIN_SIZE: (11 - 1) * 2^4 + 1
 _out_of_scope_losses = {"adaptive", "dists", "edge_loss", "lpips", "pencil_sketch", "pieapp"}
 
@@ -327,7 +337,7 @@ class SRModel(_Base):
         self._last_epoch = max_epochs
         self._log_loss_every_n_epochs = log_loss_every_n_epochs
         self._log_weights_every_n_epochs = log_weights_every_n_epochs
-        self._losses = self._create_losses(losses, patch_size, precision, loss_params)
+        self._losses = self._create_losses(losses, patch_size, precision, loss_params, channels=channels)
         self._metrics = self._create_metrics(metrics)
         if channels != 3 and ("flip" in {l.name for l in self._losses} or "FLIP" in {m for m, _ in self._metrics}):
             raise ValueError(f"the FLIP loss / metric compares colours and needs channels == 3 (got channels={channels})")
@@ -552,10 +562,11 @@ class SRModel(_Base):
         return state
 
     # -- srmodel.py:435-501 ------------------------------------------------------------------------------
-    def _create_losses(self, losses_str: str, patch_size: int, precision=32, loss_params=()) -> list[_SubLoss]:
+    def _create_losses(self, losses_str: str, patch_size: int, precision=32, loss_params=(), channels=3) -> list[_SubLoss]:
         """`loss_params`: the pixel losses' parameters as `<loss>.<key>=<value>` strings (pixel_loss.pixel_loss_parse_params), e.g.
-        ["charbonnier.eps=1e-6", "robust.alpha=-2", "robust.c=0.05"], and the focal frequency loss's `ffl.alpha=...`
-        (freq_loss.freq_loss_parse_params); an entry must name a loss of `losses_str`."""
+        ["charbonnier.eps=1e-6", "robust.alpha=-2", "robust.c=0.05"], the focal frequency loss's `ffl.alpha=...`
+        (freq_loss.freq_loss_parse_params) and the VGG loss's `vgg.weights=...`, `vgg.layer=...`, ... (vgg_loss.vgg_loss_parse_params);
+        an entry must name a loss of `losses_str`."""
         losses = []
         for loss in losses_str.split('+'):
             loss_split = loss.split('*')
@@ -581,18 +592,36 @@ class SRModel(_Base):
                                  f'got patch_size={patch_size}')
             losses.append(_SubLoss(name=loss_type, loss=fn, weight=weight))
         names = [l.name for l in losses]
-        if loss_params or any(name in _pixel_losses or name == "ffl" for name in names):
+        if "vgg" in names and channels != 3:
+            raise ValueError(f"the VGG loss compares RGB images and needs channels == 3 (got channels={channels})")
+        if loss_params or any(name in _pixel_losses or name in ("ffl", "vgg") for name in names):
             from ..freq_loss import freq_loss_parse_params
             from ..pixel_loss import pixel_loss_parse_params
-            # ffl's entries are its own (its alpha obeys another rule than robust's); every other entry, `fft.x=...` and an `ffl....`
-            # without the loss among them, is refused where it always was
-            own = [e for e in loss_params if "ffl" in names and str(e).strip().lower().partition(".")[0].strip() == "ffl"]
-            params = pixel_loss_parse_params(names, [e for e in loss_params if e not in own])
+            # ffl's entries are its own (its alpha obeys another rule than robust's), and so are vgg's (a path, names); every other entry,
+            # `fft.x=...` and an `ffl....` or `vgg....` without the loss among them, is refused where it always was
+
+            def entries_of(name):
+                return [e for e in loss_params if name in names and str(e).strip().lower().partition(".")[0].strip() == name]
+            own, own_vgg = entries_of("ffl"), entries_of("vgg")
+            params = pixel_loss_parse_params(names, [e for e in loss_params if e not in own and e not in own_vgg])
             if "ffl" in names:
                 params.update(freq_loss_parse_params(own))
             for l in losses:
                 if l.name in params:
                     l.loss = functools.partial(l.loss, **params[l.name])
+            if "vgg" in names:
+                from .. import vgg_loss
+                # one callable that owns the frozen weights, shared by every `vgg` term of the string; NOT a submodule: state_dict(),
+                # parameters() and with them the optimizers, the EMA, clipping and DDP never see it
+                vp = vgg_loss.vgg_loss_parse_params(own_vgg, _dtype_from_precision(precision))
+                pools = vgg_loss.vgg_pools(vp["net"], vp["layer"])
+                if patch_size < 2 ** pools:
+                    raise ValueError(f'loss vgg at {vp["net"]} {vp["layer"]} needs an HR patch of at least {2 ** pools} '
+                                     f'({pools} max-pools), got patch_size={patch_size}')
+                term = vgg_loss.VGGLoss(**vp)
+                for l in losses:
+                    if l.name == "vgg":
+                        l.loss = term
         return losses
 
     def _create_metrics(self, metrics: list[str]):

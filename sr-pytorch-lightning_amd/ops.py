@@ -1513,3 +1513,4 @@ from .ms_ssim_loss import *  # noqa: E402,F401,F403  MS-SSIM loss (csrc/ms_ssim_
 from .gmsd import *          # noqa: E402,F401,F403  GMSD loss and metric (csrc/gmsd.hip)
 from .pixel_loss import *    # noqa: E402,F401,F403  Charbonnier, Huber, smooth-L1, robust and PSNR losses (csrc/pixel_loss.hip)
 from .freq_loss import *     # noqa: E402,F401,F403  FFT and focal frequency losses (csrc/freq_loss.hip)
+from .vgg_loss import *      # noqa: E402,F401,F403  VGG perceptual loss on frozen weights (csrc/vgg_loss.hip around srk_conv2d)

@@ -283,7 +283,34 @@ def grad_accum_block():
     return "\n".join(out) + "\n"
 
 
-INTEGRATION_BLOCKS = {"freq_loss": freq_loss_block, "grad_accum": grad_accum_block}
+def vgg_loss_block():
+    """The tables of INTEGRATION.md "VGG perceptual loss" from the JSON lines of profiles/vgg_loss.txt (tools/microbench_vgg_loss.py):
+    the timings, then per storage dtype the worst error ratios of the HIP path against the tests' yardstick."""
+    rows = [json.loads(line) for line in (_text("vgg_loss.txt") or "").splitlines() if line.startswith("{")]
+    out = ["| net, layer | storage | shape | HIP fwd+bwd, us (min - max) | eager forms fwd+bwd, us | faster eager / HIP | peak memory of a step, MiB: HIP / eager |",
+           "|---|---|---|---|---|---|---|"]
+    for r in rows:
+        if "hip_fwd_bwd_us" not in r:
+            continue
+        forms = [k[len("eager_"):-len("_us")] for k in r if k.startswith("eager_") and k.endswith("_us") and "min_max" not in k]
+        eager = ", ".join(f"{f}: {r[f'eager_{f}_us']:,.0f}" for f in forms)
+        mem = " / ".join([f"{r['hip_peak_MiB']:,.0f}"] + [f"{r[f'eager_{f}_peak_MiB']:,.0f}" for f in forms])
+        lo, hi = r["hip_min_max_us"]
+        out.append(f"| {r['net']} `{r['layer']}` | {r['dtype']} | {r['shape']} | {r['hip_fwd_bwd_us']:,.0f} ({lo:,.0f} - {hi:,.0f}) | {eager} | "
+                   f"{r.get('ratio_faster_eager_over_hip', float('nan')):.2f} | {mem} |")
+    errs = [r for r in rows if "errors" in r]
+    if errs:
+        out += ["", "| storage | worst HIP / yardstick error ratio over all nets and layers: features | gradient | loss | cases over the tests' factor 4 |",
+                "|---|---|---|---|---|"]
+        for dt in dict.fromkeys(r["dtype"] for r in errs):
+            mine = [r for r in errs if r["dtype"] == dt]
+            over = [r["errors"] for r in mine if max(r["features_ratio"], r["gradient_ratio"], r["loss_ratio"]) > 4.0]
+            out.append(f"| {dt} | {max(r['features_ratio'] for r in mine):.2f} | {max(r['gradient_ratio'] for r in mine):.2f} | "
+                       f"{max(r['loss_ratio'] for r in mine):.2f} | {', '.join(over) if over else 'none'} |")
+    return "\n".join(out) + "\n"
+
+
+INTEGRATION_BLOCKS = {"freq_loss": freq_loss_block, "grad_accum": grad_accum_block, "vgg_loss": vgg_loss_block}
 
 
 def main():
@@ -293,7 +320,8 @@ def main():
     b, e = f"<!-- results:{tag}:begin -->\n", f"<!-- results:{tag}:end -->"
     bad = 0
     first = os.path.join(ROOT, "DESIGN.md") if tag == "r6" else os.path.join(P, "HISTORY.md")      # earlier rounds' results live in profiles/HISTORY.md
-    # tags freq_loss, grad_accum: one block each, in INTEGRATION.md (tests/test_freq_loss_cpu.py, tests/test_grad_accum_cpu.py check them)
+    # tags freq_loss, grad_accum, vgg_loss: one block each, in INTEGRATION.md (tests/test_freq_loss_cpu.py, tests/test_grad_accum_cpu.py,
+    # tests/test_vgg_loss_cpu.py check them)
     for path in ((os.path.join(ROOT, "INTEGRATION.md"),) if tag in INTEGRATION_BLOCKS else (first, os.path.join(P, "README.md"))):
         body = INTEGRATION_BLOCKS[tag]() if tag in INTEGRATION_BLOCKS else block(tag, short=(path.endswith("DESIGN.md")))
         s = open(path).read()

@@ -30,9 +30,12 @@ def parse(argv=None):
     p.add_argument("--precision", default="bf16", help="32, 16 or bf16 (Trainer key of the reference)")
     p.add_argument("--losses", default="l1", help="loss or weighted composite, e.g. l1, \"0.9*l1+0.1*flip\", \"0.9*l1+0.1*haarpsi\", \"0.16*l1+0.84*ssim\", \"0.16*l1+0.84*ms_ssim\" (--patch_size >= 161), \"0.9*l1+0.1*gmsd\"; "
                    "the pixel terms charbonnier, huber, smooth_l1, robust (needs --loss_params robust.alpha=... robust.c=...) and psnr, e.g. \"0.5*l1+0.5*charbonnier\"; "
-                   "the frequency terms fft (BasicSR's FFTLoss, unnormalised: its weight scales with the patch edge) and ffl (focal frequency loss), e.g. \"l1+0.05*fft\"")
+                   "the frequency terms fft (BasicSR's FFTLoss, unnormalised: its weight scales with the patch edge) and ffl (focal frequency loss), e.g. \"l1+0.05*fft\"; "
+                   "the perceptual term vgg on a frozen VGG-19 / VGG-16 (needs --loss_params vgg.weights=FILE), e.g. \"l1+0.006*vgg\"")
     p.add_argument("--loss_params", nargs="*", default=[], help="parameters of the pixel losses as <loss>.<key>=<value>, e.g. charbonnier.eps=1e-6 "
-                   "huber.delta=0.5 smooth_l1.beta=0.1 robust.alpha=-2 robust.c=0.05 psnr.eps=1e-8; the focal frequency loss takes ffl.alpha=1")
+                   "huber.delta=0.5 smooth_l1.beta=0.1 robust.alpha=-2 robust.c=0.05 psnr.eps=1e-8; the focal frequency loss takes ffl.alpha=1; "
+                   "the VGG loss takes vgg.weights=FILE (required: a torch.load-able state dict of torchvision's vgg19 / vgg16, never downloaded) "
+                   "vgg.net=vgg19|vgg16 vgg.layer=relu2_2 vgg.rescale=0.006 vgg.criterion=l2|l1 vgg.precision=32|16|bf16")
     p.add_argument("--metrics", nargs="+", default=None, help="validation metrics (default: the model's, PSNR SSIM); e.g. PSNR SSIM MS-SSIM FLIP GMSD")
     p.add_argument("--optimizer", default="ADAM")
     p.add_argument("--max_steps", type=int, default=100)
