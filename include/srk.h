@@ -276,9 +276,10 @@ int srk_pw_wgrad(const srk_pw_wgrad_args* a, srk_stream_t stream);
 
 /* ---- weight / bias gradient -------------------------------------------------------------------
  * Replaces autograd's conv weight-gradient for the convs above:
- *     dwp[tap][ci][co] += sum_{n,y,x} x[n][y+kh-ph][x+kw-pw][ci] * dy[n][y][x][co]   (fp32 atomics)
- *     dbp[co]          += sum dy
- * dwp/dbp are fp32 scratch the caller zeroes; srk_wgrad_finalize converts to OIHW.             */
+ *     dwp[slab][tap][ci][co] = sum over the slab's pixels of x[n][y+kh-ph][x+kw-pw][ci] * dy[n][y][x][co]
+ *     dbp[slab][co]          = sum over the slab's pixels of dy
+ * dwp/dbp are fp32 scratch that needs no zeroing: every workgroup STORES its partial sum to its own slab, and
+ * srk_wgrad_finalize sums the slabs in a fixed order and converts to OIHW (bitwise reproducible, every dtype). */
 typedef struct {
   const void* x; int x_pitch, x_coff; int x_ps;
   const void* dy; int dy_pitch, dy_coff; int dy_ps;
@@ -287,16 +288,16 @@ typedef struct {
   int KH, KW;
   float* dwp;               /* fp32 scratch: nslabs x [KH*KW][Cin][Cout]                          */
   float* dbp;               /* fp32 scratch: nslabs x [Cout], or NULL                             */
-  int nslabs;               /* value returned by srk_wgrad_slabs() for these arguments:           */
-                            /*  >0: slab mode, every workgroup stores its partial sum to its own  */
-                            /*      slab (no atomics, no zeroing, bitwise reproducible);          */
-                            /*   0: atomic mode, ONE slab that the caller has zeroed              */
+  int nslabs;               /* value returned by srk_wgrad_slabs() for these arguments (> 0):     */
+                            /* every workgroup stores its partial sum to its own slab (no         */
+                            /* atomics, no zeroing, bitwise reproducible), fp32 included          */
   int dtype;
   int cout_real;            /* the conv's real output channels (<= Cout), or 0 = unknown: large kernels   */
                             /* with few of them (cout_real * KW <= 32) put (kw, co) pairs on the MFMA columns */
 } srk_wgrad_args;
 int srk_conv2d_wgrad(const srk_wgrad_args* a, srk_stream_t stream);
-/* number of slabs srk_conv2d_wgrad will write for these arguments (0 = atomic mode, see nslabs) */
+/* number of slabs srk_conv2d_wgrad will write for these arguments (> 0 for every shape it takes; the generic kernel of fp32 and of
+ * refused 16-bit shapes writes at most 256 / (channel-block pairs): <= 9.4 MB of scratch per fp32 3x3 launch whatever Cin and Cout) */
 int srk_wgrad_slabs(const srk_wgrad_args* a);
 /* channels per (tap, ci) row of a slab (and of a dbp row): Cout, or 4 for the compact slabs of large kernels with few real output
  * channels (cout_real <= 4); the caller sizes dwp / dbp and sets srk_wgrad_finalize's CoutP with it */
@@ -319,7 +320,7 @@ int srk_wgrad_finalize(const srk_wgrad_fin_args* a, srk_stream_t stream);
  * launches of only 144 tiles at the reference's batch of 16 (configs/train_default_sr.yml:3).  The host side defers
  * them to the end of backward (torch.autograd's final callback) and issues two launches: this kernel, which walks a
  * device table of jobs with equal tile counts per workgroup whatever the layer, and srk_wgrad_finalize_group.
- *   srk_wgrad_group_ok   : 1 when `a` can be a job (16-bit, 3x3, slab mode: what srk_wgrad_slabs() > 0 means).
+ *   srk_wgrad_group_ok   : 1 when `a` can be a job (16-bit, 3x3, a shape the DMA slab kernel "wgrad_ws" takes).
  *   srk_wgrad_group_plan : in : jobs[i] with dbp != NULL where a bias gradient is wanted; `scratch` NULL = sizing pass.
  *                          out: jobs[i].nslabs, *nblocks, *scratch_floats; with `scratch` (device, fp32, that many floats)
  *                               also jobs[i].dwp / dbp (slab regions inside it) and, when given, the HOST images of the
@@ -1335,7 +1336,7 @@ int srk_vgg_image_grad(const srk_vgg_image_grad_args* a, srk_stream_t stream);
 const char* srk_last_error(void);
 /* Name of the kernel family the calling thread launched last through srk_conv2d, srk_conv2d_wgrad or srk_unfold_nchw ("" before the
  * first): a thread-local pointer to a string literal, e.g. "conv_ws<2,4,1,1>", "conv_ws<2,4,0,0>x4" (four accumulating passes over a
- * pixel-shuffled input), "conv_igemm<64,3>", "conv_ks", "lk5_fwd", "wgrad_atomic<3>".  The names tell apart what the dispatch tells apart;
+ * pixel-shuffled input), "conv_igemm<64,3>", "conv_ks", "lk5_fwd", "wgrad_generic<3>".  The names tell apart what the dispatch tells apart;
  * the tests assert on them which side of a dispatch decision ran. */
 const char* srk_last_kernel(void);
 int srk_version(void);

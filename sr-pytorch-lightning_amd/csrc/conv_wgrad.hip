@@ -8,8 +8,10 @@
 // (4 pixels x 16 channels per 16-lane group); the fp32 path reads one float per lane (32x32x2 MFMA).
 // One K-step = one 16-pixel tile row; the K*K taps are K*K accumulator tiles fed from shifted rows /
 // columns of the halo image.  A workgroup owns one (ci-block, co-block) pair of 128-byte channel
-// blocks, walks a strided set of 16x16 pixel tiles accumulating in registers, and adds its partial
-// result into the fp32 scratch with row-contiguous float atomics.
+// blocks, walks a strided set of 16x16 pixel tiles accumulating in registers, and STORES its partial
+// result to its own slab of the fp32 scratch (blockIdx.x; the fp32 path's four K-group waves first meet
+// in LDS in wave order).  srk_wgrad_finalize sums the slabs in slab order: no atomics, nothing to zero,
+// bitwise reproducible, like the slab kernels below.
 //
 // Replaces: autograd's conv2d weight/bias gradient for models/common.py:7-30 convs.
 #include <stdlib.h>
@@ -197,22 +199,57 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const srk_wgrad_args
     }
   }
 
-  // ---- add the partial result into the fp32 scratch (row-contiguous float atomics) -------------------
+  // ---- fp32: the K-group waves hold partial sums of the SAME 32 x 32 block; they meet in LDS in wave order -------------
+  // ((k0 + k1) + k2) + k3, one wave's 36 KB of accumulators at a time: fits the tile buffers, fixed order, bitwise reproducible
+  float* const red = reinterpret_cast<float*>(smem);
+  static_assert((C::KGROUPS > 1 ? C::NTAPS * 16 * 64 * 4 : 0) <= C::LDS_BYTES && C::NT * 4 <= C::LDS_BYTES, "reduction buffers exceed the tile buffers");
+  if constexpr (C::KGROUPS > 1) {
+#pragma unroll 1
+    for (int g = 1; g < C::KGROUPS; ++g) {
+      __syncthreads();   // the last tile's fragment reads / the previous round's adds are done
+      if (kgroup == g) {
+#pragma unroll
+        for (int t = 0; t < C::NTAPS; ++t)
+#pragma unroll
+          for (int e = 0; e < 16; ++e) red[(t * 16 + e) * 64 + lane] = acc[t][e];
+      }
+      __syncthreads();
+      if (kgroup == 0) {
+#pragma unroll
+        for (int t = 0; t < C::NTAPS; ++t)
+#pragma unroll
+          for (int e = 0; e < 16; ++e) acc[t][e] += red[(t * 16 + e) * 64 + lane];
+      }
+    }
+  }
+
+  // ---- store the workgroup's partial result to ITS slab (blockIdx.x): no atomics, nothing to zero; srk_wgrad_finalize sums the slabs ----
+  const int slot = blockIdx.x;
   const int co = cob * C::CBLK + cbk * 32 + (lane & 31);
   const int hq = lane >> 5;
-  if (co < a.Cout) {
+  if (kgroup == 0 && co < a.Cout) {
+    float* const slab = a.dwp + (size_t)slot * ((size_t)C::NTAPS * a.Cin * a.Cout);
 #pragma unroll
     for (int t = 0; t < C::NTAPS; ++t) {
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
         const int ci = cib * C::CBLK + rb * 32 + (e & 3) + 8 * (e >> 2) + 4 * hq;
-        if (ci < a.Cin) atomicAdd(a.dwp + ((size_t)t * a.Cin + ci) * a.Cout + co, acc[t][e]);
+        if (ci < a.Cin) slab[((size_t)t * a.Cin + ci) * a.Cout + co] = acc[t][e];
       }
     }
   }
   if (a.dbp && cib == 0) {
-    const int c = cob * C::CBLK + b_c;
-    if (c < a.Cout) atomicAdd(a.dbp + c, bsum);
+    // bias: the BPARTS pixel partitions of a channel summed in partition order
+    __syncthreads();     // the accumulator rounds (fp32) / the last tile's fragment reads (16-bit) are done with the buffers
+    red[tid] = bsum;     // [b_part][b_c]
+    __syncthreads();
+    if (tid < C::CBLK) {
+      float t = 0.f;
+#pragma unroll
+      for (int p = 0; p < BPARTS; ++p) t += red[p * C::CBLK + tid];
+      const int c = cob * C::CBLK + tid;
+      if (c < a.Cout) a.dbp[(size_t)slot * a.Cout + c] = t;
+    }
   }
 }
 
@@ -1067,7 +1104,7 @@ __global__ __launch_bounds__(256, 1) void wgrad1x1_small_kernel(const srk_wgrad_
   }
 }
 
-// pixel slabs used by the slab-mode kernel for these arguments (0: atomic-mode kernel)
+// pixel slabs used by the DMA slab kernels for these arguments (0: the generic kernel, conv_wgrad_kernel, takes the shape)
 // 1x1 slab kernel: tile shape (ci blocks x co blocks of 64) and slab count
 static void wgrad1x1_shape(const srk_wgrad_args& a, int& cib, int& cob) {
   if (a.Cout >= a.Cin) { cib = 2; cob = 4; } else { cib = 4; cob = 2; }
@@ -1095,6 +1132,20 @@ static int ws_tile_height(long long n_images, int H, int W) {
   static const int forced = [] { const char* e = srk_dbg_getenv("SRK_WGRAD_TH"); return e ? atoi(e) : 0; }();
   if (forced == 8 || forced == 16) return forced;
   return n_images * ((H + 15) / 16) * ((W + 15) / 16) >= 1024 ? WS_TH : 16;
+}
+
+// Grid and slab count of the generic kernel (fp32; 16-bit shapes the DMA slab kernels refuse): one slab per blockIdx.x.  With channel blocks of
+// CBLK (32 fp32 / 64 16-bit) the count is at most 256 / (cib * cob), so the scratch of a launch is at most 256 * taps * CBLK * CBLK floats whatever
+// Cin and Cout are: 9.4 MB for a fp32 3x3 (37.7 MB 16-bit, the slab kernels' own bound); beyond 256 block pairs it is one slab, the gradient's size.
+static int wgrad_generic_slabs(const srk_wgrad_args& a) {
+  if (a.KH != a.KW || (a.KH != 1 && a.KH != 3)) return 0;
+  const int cblk = a.dtype == SRK_F32 ? 32 : 64;
+  const long long ntiles = (long long)a.N * ((a.H + 15) / 16) * ((a.W + 15) / 16);
+  const long long pairs = (long long)((a.Cin + cblk - 1) / cblk) * ((a.Cout + cblk - 1) / cblk);
+  long long slabs = pairs > 0 ? 256 / pairs : 0;
+  if (slabs < 1) slabs = 1;
+  if (slabs > ntiles) slabs = ntiles;
+  return slabs > 0 ? (int)slabs : 0;
 }
 
 static int wgrad_ws_slabs(const srk_wgrad_args& a) {
@@ -1203,10 +1254,8 @@ template <int DT, int KS> int launch(const srk_wgrad_args& a, hipStream_t st) {
     return SRK_E_BADARG;
   }
   const int cib = (a.Cin + C::CBLK - 1) / C::CBLK, cob = (a.Cout + C::CBLK - 1) / C::CBLK;
-  int slabs = 256 / (cib * cob);
-  if (slabs < 1) slabs = 1;
-  if (slabs > ntiles) slabs = (int)ntiles;
-  srk_kernel_name = KS == 3 ? "wgrad_atomic<3>" : "wgrad_atomic<1>";
+  const int slabs = wgrad_generic_slabs(a);          // = a.nslabs (checked by the caller): one slab per blockIdx.x
+  srk_kernel_name = KS == 3 ? "wgrad_generic<3>" : "wgrad_generic<1>";
   hipLaunchKernelGGL((conv_wgrad_kernel<DT, KS>), dim3(slabs, cib, cob), dim3(C::NT), C::LDS_BYTES, st, a, tilesX, tilesY,
                      (int)ntiles);
   SRK_LAUNCH_CHECK();
@@ -1232,11 +1281,12 @@ extern "C" int srk_conv2d_wgrad(const srk_wgrad_args* a, srk_stream_t stream) {
   SRK_CHECK_ARG(a->Cin % (rx * rx) == 0 && (a->Cin / (rx * rx)) % ch == 0 && a->Cout % (rd * rd) == 0 && (a->Cout / (rd * rd)) % ch == 0,
                 "srk_conv2d_wgrad: pixel-shuffled operand incompatible with channel count");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int slabs = wgrad_ws_slabs(*a);
-  SRK_CHECK_ARG(a->nslabs == slabs, "srk_conv2d_wgrad: nslabs=%d but srk_wgrad_slabs() is %d for these arguments", a->nslabs, slabs);
+  const int ws = wgrad_ws_slabs(*a);                 // > 0: a DMA slab kernel takes the shape
+  const int slabs = ws > 0 ? ws : wgrad_generic_slabs(*a);
+  SRK_CHECK_ARG(a->nslabs == slabs && slabs > 0, "srk_conv2d_wgrad: nslabs=%d but srk_wgrad_slabs() is %d for these arguments", a->nslabs, slabs);
   if (a->KH > 3) return srk_wgrad_lk_launch(*a, st);
-  if (slabs > 0 && a->KH == 1) return a->dtype == SRK_BF16 ? launch_1x1_any<SRK_BF16>(*a, st, slabs) : launch_1x1_any<SRK_F16>(*a, st, slabs);
-  if (slabs > 0) return a->dtype == SRK_BF16 ? launch_ws<SRK_BF16>(*a, st, slabs) : launch_ws<SRK_F16>(*a, st, slabs);
+  if (ws > 0 && a->KH == 1) return a->dtype == SRK_BF16 ? launch_1x1_any<SRK_BF16>(*a, st, slabs) : launch_1x1_any<SRK_F16>(*a, st, slabs);
+  if (ws > 0) return a->dtype == SRK_BF16 ? launch_ws<SRK_BF16>(*a, st, slabs) : launch_ws<SRK_F16>(*a, st, slabs);
   switch (a->dtype) {
     case SRK_BF16: return dispatch<SRK_BF16>(*a, st);
     case SRK_F16: return dispatch<SRK_F16>(*a, st);
@@ -1244,7 +1294,11 @@ extern "C" int srk_conv2d_wgrad(const srk_wgrad_args* a, srk_stream_t stream) {
   }
 }
 
-extern "C" int srk_wgrad_slabs(const srk_wgrad_args* a) { return a ? wgrad_ws_slabs(*a) : 0; }
+extern "C" int srk_wgrad_slabs(const srk_wgrad_args* a) {
+  if (!a) return 0;
+  const int ws = wgrad_ws_slabs(*a);
+  return ws > 0 ? ws : wgrad_generic_slabs(*a);
+}
 extern "C" int srk_wgrad_slab_cout(const srk_wgrad_args* a) {
   if (!a) return 0;
   return (a->KH > 3 && srk_wgrad_lk_ok(*a)) ? srk_wgrad_lk_slab_cout(*a) : a->Cout;
@@ -1254,7 +1308,7 @@ extern "C" int srk_wgrad_slab_cout(const srk_wgrad_args* a) {
 extern "C" int srk_wgrad_group_job_bytes(void) { return (int)sizeof(WgJob); }
 
 extern "C" int srk_wgrad_group_ok(const srk_wgrad_args* a) {
-  // jobs the grouped kernel takes: what the 3x3 slab kernel takes
+  // jobs the grouped kernel takes: what the 3x3 DMA slab kernel takes (not the generic kernel's shapes)
   return (a && a->KH == 3 && a->KW == 3 && a->N > 0 && wgrad_ws_slabs(*a) > 0) ? 1 : 0;
 }
 

@@ -299,12 +299,11 @@ def wgrad_raw(x, dy, *, N, H, W, Cin, Cout, k, w_shape, ps_r=0, scale=1.0, x_ps=
     nslabs = L.load().srk_wgrad_slabs(a)
     couts = L.load().srk_wgrad_slab_cout(a)     # channels per slab row: Cout, or 4 (compact slabs: large kernel, <= 4 real output channels)
     per = k * k * Cin * couts
-    if nslabs > 0:      # slab mode: every workgroup writes its own slab, nothing to zero
-        scratch = torch.empty(nslabs * (per + couts), dtype=torch.float32, device=dev)
-    else:               # atomic mode: one zeroed slab
-        scratch = torch.zeros(per + couts, dtype=torch.float32, device=dev)
-    ns = max(nslabs, 1)
-    dbp = scratch[ns * per:]
+    if nslabs <= 0:
+        raise RuntimeError(f"srk_wgrad_slabs: no weight-gradient kernel for a {k}x{k} convolution {Cin} -> {Cout} in {x.dtype}")
+    # every workgroup writes its own slab, in every dtype: nothing to zero, srk_wgrad_finalize sums the slabs in a fixed order
+    scratch = torch.empty(nslabs * (per + couts), dtype=torch.float32, device=dev)
+    dbp = scratch[nslabs * per:]
     a.dwp, a.dbp, a.nslabs = scratch.data_ptr(), (dbp.data_ptr() if want_bias else 0), nslabs
     L.call("srk_conv2d_wgrad", a, _stream())
     dw = out_w if out_w is not None else torch.empty(w_shape, dtype=torch.float32, device=dev)

@@ -12,8 +12,8 @@ names only: the parent (test_gpu_dispatch_sides.py) asserts that a fallback's na
 Criteria are those of the existing test of the same operation, unchanged (each group names its source).  Two bounds are derived:
 
 * the r*r-pass data gradient through a PixelShuffle (`ps_dgrad`): see its docstring;
-* the atomic-mode weight gradient: its summation order is free, the bound is the project's fp32-accumulation bound of
-  test_grouped_matches_per_layer_and_float64 / test_wgrad_1x1_slab_kernel, on both of two runs.
+* the generic weight gradient (one slab per workgroup, summed in a fixed order): the bound is the project's fp32-accumulation bound of
+  test_grouped_matches_per_layer_and_float64 / test_wgrad_1x1_slab_kernel, on both of two runs, and the two runs are equal bit for bit.
 
 This module is a plain helper (no fixtures, no pytest hooks); importing it needs no GPU (tests/test_dispatch_knobs.py reads SETTINGS)."""
 import json
@@ -155,10 +155,17 @@ def ws_epilogue(R, setting, check, variants):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
-# wgrad_raw, atomic mode -- criteria: test_gpu_wgrad_group.py::test_grouped_matches_per_layer_and_float64 (3x3: 1e-4 of the largest
-# entry) and test_gpu_ws_epilogue.py::test_wgrad_1x1_slab_kernel (1x1: 2e-5 * max(1, largest entry)); two runs, both bounded
+# wgrad_raw, the generic kernel -- criteria: test_gpu_wgrad_group.py::test_grouped_matches_per_layer_and_float64 (3x3: 1e-4 of the largest
+# entry) and test_gpu_ws_epilogue.py::test_wgrad_1x1_slab_kernel (1x1: 2e-5 * max(1, largest entry)); two runs, both bounded, and equal
+# bit for bit (`run_to_run`: the largest difference, NaN-proof through the integer view)
 # ---------------------------------------------------------------------------------------------------------------------------------
-def wgrad_atomic(R, setting, check):
+def generic_slabs(n, h, w, cin, cout):
+    """The generic kernel's grid over 16 x 16 pixel tiles and 64-channel blocks (16-bit): one slab per blockIdx.x."""
+    tiles = n * ((h + 15) // 16) * ((w + 15) // 16)
+    return max(1, min(tiles, 256 // (((cin + 63) // 64) * ((cout + 63) // 64))))
+
+
+def wgrad_generic(R, setting, check):
     import torch
     import sr_amd as A
     out_cases = {}
@@ -181,21 +188,24 @@ def wgrad_atomic(R, setting, check):
                 kerns.append(log[-1][1])
                 slabs.append(log[-1][2])
                 nan = nan or not bool(torch.isfinite(dw).all() and torch.isfinite(db).all())
-                runs.append((dw.double().cpu(), db.double().cpu()))
+                runs.append((dw.double().cpu(), db.double().cpu(), dw.view(torch.int32).cpu(), db.view(torch.int32).cpu()))
             kern = {"wgrad": kerns[0], "wgrad_second_run": kerns[1]}
-            expect = {"wgrad": f"wgrad_atomic<{k}>", "wgrad_second_run": f"wgrad_atomic<{k}>"} if setting == "SRK_NO_WS" else {}
-            cid = f"wgrad_atomic/{_dtname(dt)}/k{k}/{n}x{h}x{w}/{cin}to{cout}"
+            expect = {"wgrad": f"wgrad_generic<{k}>", "wgrad_second_run": f"wgrad_generic<{k}>"} if setting == "SRK_NO_WS" else {}
+            cid = f"wgrad_generic/{_dtname(dt)}/k{k}/{n}x{h}x{w}/{cin}to{cout}"
             if not check:
                 out_cases[cid] = _case(kern, expect, nan, nslabs=slabs)
                 continue
+            want_slabs = generic_slabs(n, h, w, cin, cout)
             ref_w = torch.nn.grad.conv2d_weight(x.double().cpu().permute(0, 3, 1, 2), (cout, cin, k, k), dy.double().cpu().permute(0, 3, 1, 2), padding=k // 2)
             ref_b = dy.double().cpu().sum((0, 1, 2))
             if k == 3:
                 tw, tb = 1e-4 * float(ref_w.abs().max()), 1e-4 * float(ref_b.abs().max())
             else:
                 tw, tb = 2e-5 * max(1.0, float(ref_w.abs().max())), 2e-5 * max(1.0, float(ref_b.abs().max()))
-            ratio = max(max(float((dw - ref_w).abs().max()) / tw, float((db - ref_b).abs().max()) / tb) for (dw, db) in runs)
-            out_cases[cid] = _case(kern, expect, nan, ratio, nslabs=slabs, run_to_run=float((runs[0][0] - runs[1][0]).abs().max()))
+            ratio = max(max(float((dw - ref_w).abs().max()) / tw, float((db - ref_b).abs().max()) / tb) for (dw, db, _, _) in runs)
+            same = torch.equal(runs[0][2], runs[1][2]) and torch.equal(runs[0][3], runs[1][3])
+            out_cases[cid] = _case(kern, expect, nan, ratio, nslabs=slabs, nslabs_generic=[want_slabs, want_slabs], bitwise_repeat=bool(same),
+                                   run_to_run=float((runs[0][0] - runs[1][0]).abs().max()))
     return out_cases
 
 
@@ -668,7 +678,7 @@ def _g(fn, **kw):
 
 
 SETTINGS = {
-    "SRK_NO_WS": ({"SRK_NO_WS": "1"}, [_g(ws_epilogue, variants=WS_VARIANTS), _g(wgrad_atomic)], 240),
+    "SRK_NO_WS": ({"SRK_NO_WS": "1"}, [_g(ws_epilogue, variants=WS_VARIANTS), _g(wgrad_generic)], 240),
     "SRK_NO_EARLY": ({"SRK_NO_EARLY": "1"}, [_g(ws_epilogue, variants=WS_EARLY_VARIANTS)], 180),
     "SRK_NO_KS": ({"SRK_NO_KS": "1"}, [_g(ks_forms), _g(ks_slices), _g(ks_ps_store), _g(ps_dgrad)], 300),
     "SRK_PS_DGRAD_WS": ({"SRK_PS_DGRAD_WS": "1"}, [_g(ps_dgrad)], 180),
@@ -682,7 +692,7 @@ SETTINGS = {
     "SRK_UNFOLD_PX": ({"SRK_UNFOLD_PX": "1"}, [_g(unfold_px)], 120),
 }
 # the no-knob child launches the union of all cases (names only, no float64 work)
-NONE_GROUPS = [_g(ws_epilogue, variants=WS_VARIANTS), _g(wgrad_atomic), _g(ks_forms), _g(ks_slices), _g(ks_ps_store), _g(ps_dgrad), _g(p1_forms),
+NONE_GROUPS = [_g(ws_epilogue, variants=WS_VARIANTS), _g(wgrad_generic), _g(ks_forms), _g(ks_slices), _g(ks_ps_store), _g(ps_dgrad), _g(p1_forms),
                _g(collapsed_fwd, shapes=COLLAPSED_ALL + [s for s in COLLAPSED_ROWS if s not in COLLAPSED_ALL]),
                _g(lk_elements, shapes=LK_5X5 + LK_WGRAD), _g(unfold_px)]
 NONE_TIMEOUT = 240

@@ -6,8 +6,9 @@ bodies, the criteria -- those of the existing test of the same operation -- and 
 
 Every case is checked in this order:
 1. premise: srk_last_kernel() named the fallback, and the same call with no knob (the child "none") named another kernel -- a misspelt
-   or retired knob cannot pass by running the preferred side twice; under SRK_NO_WS the weight gradient also ran with
-   srk_wgrad_slabs() == 0;
+   or retired knob cannot pass by running the preferred side twice; under SRK_NO_WS the weight gradient also ran with the generic
+   kernel's own slab count (one slab per workgroup of its grid, worked out in dispatch_cases.generic_slabs) where the no-knob run used
+   the slab kernels' count, and its two runs are equal bit for bit;
 2. coverage: no NaN of the prefilled outputs survived;
 3. numbers: the worst error is within its bound.
 
@@ -94,8 +95,10 @@ def test_fallback_side_against_float64(setting):
                 bad.append((cid, role, "the no-knob run took the same kernel", want))
             else:
                 moved += 1
-        if "nslabs" in c and not (c["nslabs"] == [0, 0] and all(s > 0 for s in base[cid]["nslabs"])):
-            bad.append((cid, "srk_wgrad_slabs()", c["nslabs"], "no knob", base[cid]["nslabs"]))
+        if "nslabs" in c and not (c["nslabs"] == c["nslabs_generic"] and all(s > 0 for s in c["nslabs"] + base[cid]["nslabs"])):
+            bad.append((cid, "srk_wgrad_slabs()", c["nslabs"], "generic grid", c["nslabs_generic"], "no knob", base[cid]["nslabs"]))
+        if "nslabs" in c and not c["bitwise_repeat"]:
+            bad.append((cid, "two runs of the generic weight gradient differ", c["run_to_run"]))
         # 2. coverage
         if c["nan"]:
             bad.append((cid, "a NaN of the prefilled output survived (or the kernel made one)"))

@@ -252,12 +252,10 @@ def test_manual_set_lr_between_two_replays_needs_no_recapture(A):
 
 # ---- Trainer.fit -----------------------------------------------------------------------------------------------------------------------------
 # The smallest model and batch tests/test_gpu_trainer_graph.py trains (EDSR x2, 32 features, 2 blocks, 8 patches of 24x24).  Bit-for-bit
-# comparisons of two training runs run in bf16, train.py's default precision: the 16-bit weight gradients are summed in slab order
-# (include/srk.h: "bitwise reproducible"), so a run repeats itself bit for bit.  The fp32 weight gradient (csrc/conv_wgrad.hip, atomic
-# mode) accumulates with fp32 atomics in whatever order the workgroups arrive: two launch-by-launch fp32 runs of the same 12 steps
-# already part from each other (measured: the gradients of ONE backward pass computed twice differ in all 16 tensors; final parameters
-# of two eager runs differ by up to 6.6e-6 under Adam, 3.7e-9 under SGD, with and without a schedule), so fp32 is checked for
-# everything but the bits of the weights.
+# comparisons of two training runs run in bf16, train.py's default precision: the weight gradients are summed in slab order
+# (include/srk.h: "bitwise reproducible"), so a run repeats itself bit for bit.  When these tests were written the fp32 weight gradient
+# (csrc/conv_wgrad.hip) still accumulated with float atomics, so fp32 is checked here for everything but the bits of the weights; it
+# writes slabs now, and tests/test_gpu_step_reproducible.py holds fp32 runs to their bits.
 def _fit(A, use_graph, optimizer, first, last, state=None, weights=None, precision="bf16"):
     """Trainer.fit over batches [first, last), lr halving every second step."""
     from sr_amd import trainer as T

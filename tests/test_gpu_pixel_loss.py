@@ -280,9 +280,10 @@ def test_graphed_step_follows_the_eager_loop(A, monkeypatch, losses, loss_params
     assert g is not None and g.graphs is not None and not g.failed, "the step with the pixel loss was captured"
     lg, le = tg.losses, te.losses
     assert len(lg) == len(le) == 8 and all(np.isfinite(lg))
-    np.testing.assert_allclose(lg, le, rtol=2e-4)
+    # every launch of the step sums in a fixed order ("Reproducibility"): the replayed step gives the eager loop's bits
+    assert np.array_equal(np.asarray(lg, np.float32).view(np.int32), np.asarray(le, np.float32).view(np.int32)), (lg, le)
     diffs = [float((a - b).abs().max()) for a, b in zip(pg, pe)]
     print(f"\n{losses}: largest parameter difference {max(diffs):.2e} (tensor {diffs.index(max(diffs))} of {len(diffs)})")
-    for a, d in zip(pg, diffs):
+    for a, b in zip(pg, pe):
         assert torch.isfinite(a).all()
-        assert d <= 2e-4, diffs
+        assert torch.equal(a.view(torch.int32), b.view(torch.int32)), diffs

@@ -143,7 +143,8 @@ def test_graphed_step_with_ssim_follows_the_eager_loop(A):
     assert g is not None and g.graphs is not None and not g.failed, "the step with the SSIM loss was captured"
     lg, le = tg.losses, te.losses
     assert len(lg) == len(le) == 8 and all(np.isfinite(lg))
-    np.testing.assert_allclose(lg, le, rtol=2e-4)
+    # every launch of the step sums in a fixed order ("Reproducibility"): the replayed step gives the eager loop's bits
+    assert np.array_equal(np.asarray(lg, np.float32).view(np.int32), np.asarray(le, np.float32).view(np.int32)), (lg, le)
     for a, b in zip(pg, pe):
         assert torch.isfinite(a).all()
-        assert float((a - b).abs().max()) <= 2e-4, float((a - b).abs().max())
+        assert torch.equal(a.view(torch.int32), b.view(torch.int32)), float((a - b).abs().max())

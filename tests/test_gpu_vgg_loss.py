@@ -269,9 +269,13 @@ def test_trainer_fit_graph_on_and_off(A, precision, tmp_path):
     (lg, pg, g), (le, pe, _) = out
     assert g is not None and g.graphs is not None and not g.failed, "the step was captured"
     assert len(lg) == len(le) == 10 and all(np.isfinite(lg))
-    np.testing.assert_allclose(lg, le, rtol=2e-4 if precision == 32 else 2e-3)
+    if precision == 32:
+        # every launch of the step sums in a fixed order ("Reproducibility"): the replayed step gives the eager loop's bits
+        assert np.array_equal(np.asarray(lg, np.float32).view(np.int32), np.asarray(le, np.float32).view(np.int32)), (lg, le)
+    else:
+        np.testing.assert_allclose(lg, le, rtol=2e-3)
     for a, b in zip(pg, pe):
         if precision == 32:
-            assert float((a - b).abs().max()) <= 2e-4, float((a - b).abs().max())
+            assert torch.equal(a.view(torch.int32), b.view(torch.int32)), float((a - b).abs().max())
         else:
             assert float((a - b).abs().max()) <= 9.5e-3 and float((a - b).abs().mean()) <= 3e-4
